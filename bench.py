@@ -3,14 +3,17 @@
 
 One "step" = the whole hot path (QP->LDP setup, dual active-set iteration, back-transform) over one batch of synthetic
 QPs per GPU, inputs already resident in HBM, results left in HBM.  The headline (`value`) is BASELINE.json's metric:
-config C2, 100 000 QPs per GPU, n=50 m=150.  The same JSON line carries the other BASELINE configs under "configs"
-(C3: MPC-size QPs n=12 m=48 ms=12; C4: n=200 m=600; C5: warm-started sequence on the C2 batch), each with its own
-throughput, solve-kernel roofline, CPU baseline sample and parity against that CPU run.
+config C2, 100 000 QPs per GPU, n=50 m=150.  A plain run sets up, warms up, times the steps and prints the line.  With
+--full the same JSON line carries the other BASELINE configs under "configs" (C3: MPC-size QPs n=12 m=48 ms=12; C4:
+n=200 m=600; C5: warm-started sequence on the C2 batch), each with its own throughput, solve-kernel roofline, CPU baseline
+sample and parity against that CPU run, plus the batch sweep, the exact-mode steps and the host transfer times.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (inputs are seeded: the same in every run).
 
 One process per GPU; independent QPs are sharded across ranks with no data-path collective; the only communication is
 the barrier + MAX of the elapsed time the contract asks for.
 
     python bench.py --gpus 1 --steps 20 --warmup 2
+    python bench.py --gpus 1 --steps 20 --warmup 2 --full                 # + side configs, CPU baseline, sweep, exact mode
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
            bench.py --gpus 8 --steps 20 --warmup 2                      # weak scaling: 100k C2 QPs per GPU
     ... bench.py --gpus 8 --config C3 --strong                          # ONE 1M-QP C3 batch, QP k on rank k mod 8
@@ -318,7 +321,7 @@ class Runner:
             parts.append({k: v[mine] for k, v in g.items()})
         return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
 
-    def run(self, cfg, steps, warmup, batch=None, strong=False, cpu_sample=-1, thread_options=None, exact_steps=0):
+    def run(self, cfg, steps, warmup, batch=None, strong=False, cpu_sample=-1, thread_options=None, exact_steps=0, probe_passes=True):
         import daqp_amd
         from daqp_amd.parallel import max_over_ranks
         torch = self.torch
@@ -383,7 +386,7 @@ class Runner:
         elapsed = time.perf_counter() - t0
         elapsed = max_over_ranks(elapsed, device=self.red_device)
         probe = None
-        if warm and self.rank == 0:
+        if warm and self.rank == 0 and probe_passes:
             # the steps of a pass differ (working sets grow along the walk, the way back ends on the cold optimum): the launch time quoted for the
             # roofline is the mean over ONE forward and ONE backward pass, sampled step by step outside the timed region (a sample waits for the device)
             probe = []
@@ -418,7 +421,7 @@ class Runner:
         rechecked = int(bm.rechecked())   # problems of the last step whose INFEASIBLE verdict took the second pass in the reference's arithmetic: none here
         return q, res, bm, dict(N=N, N_total=N_total, rechecked=rechecked, elapsed=elapsed, setup_ms=setup_ms, solve_ms=solve_ms, T=T if warm else 1, fs=fs, exact=exact, probe=probe)
 
-    def report(self, cfg, q, res, info, steps, cpu_sample, headline):
+    def report(self, cfg, q, res, info, steps, cpu_sample, headline, transfers=True):
         """rank 0: the JSON fields of one configuration"""
         c = CONFIGS[cfg]
         n, m, ms = c["n"], c["m"], c["ms"]
@@ -462,7 +465,7 @@ class Runner:
         }
         if info.get("exact"):
             out["exact"] = info["exact"]
-        if self.world == 1:
+        if self.world == 1 and transfers:
             try:
                 out["transfers"] = transfer_times(self.torch, q if not warm else dict(q, f=info["fs"][0]), res, N, warm)
                 tr = out["transfers"]
@@ -732,6 +735,28 @@ def emit(line, args):
     print(text, flush=True)
 
 
+DUMP_NAMES = ("x", "lam", "fval", "soft_slack", "exitflag", "iter")
+DUMP_BYTES = 60 << 20       # --dump-outputs writes at most this much
+DUMP_SEED = 20250101
+
+
+def dump_outputs(path, parts):
+    """--dump-outputs: what the timed path handed its caller in its LAST timed step -- x, lam, fval, soft_slack, exitflag, iter -- as
+    <path>/<name>.npy in float64.  `parts` are the result dicts of that step (one per shard, concatenated in order).  Every problem when the
+    whole batch fits in DUMP_BYTES, else the same fixed sample of problems in every run (seed DUMP_SEED, ascending problem index)."""
+    N = sum(int(p_["x"].shape[0]) for p_ in parts)
+    per_qp = 8 * sum(int(np.prod(tuple(parts[0][k].shape[1:]))) for k in DUMP_NAMES)
+    idx = None
+    if N * per_qp > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, DUMP_BYTES // per_qp, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for k in DUMP_NAMES:
+        v = np.concatenate([p_[k].cpu().numpy() for p_ in parts])
+        if idx is not None:
+            v = v[idx]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def launch_plan(gpus, env, argv):
     """What `bench.py --gpus N` has to do about ranks.  Under a torch.distributed launcher (WORLD_SIZE set) the launcher's world
     size must BE --gpus (anything else is a mis-launch and fails loudly); without one, N == 1 runs in this process (returns
@@ -828,6 +853,8 @@ def multi_entry(args):
                          "achieved": None, "peak": HBM_PEAK_GBS if BOUND[cfg] == "hbm" else VALU_PEAK_GCYC, "frac": None, "traffic": None,
                          "note": "counter-derived figures are quoted by the rank-per-GPU line (same kernels, same batch per device)"},
             "checks": {"all_optimal": ok, "max_abs_x_minus_analytic_optimum": dx}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     mb.close()
     emit(line, args)
     return 0
@@ -841,8 +868,12 @@ def main():
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS), help="the configuration `value` is quoted on (BASELINE headline: C2)")
     ap.add_argument("--batch", type=int, default=0, help="QPs per GPU per step (0: the config's own; with --strong: in total)")
     ap.add_argument("--strong", action="store_true", help="ONE batch split over the ranks (QP k -> rank k mod G) instead of one batch per rank")
-    ap.add_argument("--side-configs", default="auto", help="comma list of further configs reported under \"configs\" (auto: C3,C4,C5 at N=1 for the C2 headline; none)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="QPs for the CPU baseline (-1: auto, 0: skip)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: the other configs, the CPU baseline and its parity sample, the "
+                    "batch sweep, the exact-mode steps, host transfers and C5's probe passes (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (x, lam, fval, "
+                    "soft_slack, exitflag, iter; float64; a fixed sample of the problems beyond 60 MB) as DIR/<name>.npy")
+    ap.add_argument("--side-configs", default="auto", help="comma list of further configs reported under \"configs\" (auto: C3,C4,C5 with --full at N=1 for the C2 headline; none)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="QPs for the CPU baseline (-1: auto, a sample with --full and none without; 0: skip)")
     ap.add_argument("--single-device", action="store_true", help="every rank uses cuda:0 (multi-rank smoke test on a 1-GPU box; use --backend gloo)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--no-sweep", action="store_true", help="skip the batch-size sweep of the headline configuration (reported under \"batch_sweep\")")
@@ -864,15 +895,18 @@ def main():
 
     R = Runner(args)
     auto_sample = {"C2": 65536, "C3": 262144, "C4": 1024, "C5": 8192}   # ~10-25 CPU-seconds each on one core-group
-    sample = lambda cfg: 0 if (args.cpu_sample == 0 or R.world > 1) else (auto_sample[cfg] if args.cpu_sample < 0 else args.cpu_sample)
+    sample = lambda cfg: 0 if (args.cpu_sample == 0 or R.world > 1 or (args.cpu_sample < 0 and not args.full)) else (
+        auto_sample[cfg] if args.cpu_sample < 0 else args.cpu_sample)
 
     exact_steps = {"C2": 3, "C3": 5, "C4": 1, "C5": 0}
-    want_exact = (not args.no_exact) and R.world == 1
+    want_exact = args.full and (not args.no_exact) and R.world == 1
     q, res, bm, info = R.run(args.config, args.steps, args.warmup, batch=args.batch or None, strong=args.strong,
-                             exact_steps=exact_steps[args.config] if want_exact else 0)
+                             exact_steps=exact_steps[args.config] if want_exact else 0, probe_passes=args.full)
+    if args.dump_outputs and R.rank == 0:
+        dump_outputs(args.dump_outputs, [res])
     line = None
     if R.rank == 0:
-        h = R.report(args.config, q, res, info, args.steps, sample(args.config), headline=True)
+        h = R.report(args.config, q, res, info, args.steps, sample(args.config), headline=True, transfers=args.full)
         line = {
             "metric": h["metric"], "value": h["value"], "unit": h["unit"], "n_gpus": R.world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": h["ms_per_step"], "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
@@ -891,7 +925,7 @@ def main():
     del q, res, bm
     R.torch.cuda.empty_cache()
 
-    if R.world == 1 and args.config == "C2" and not args.batch and not args.strong and not args.no_sweep:
+    if args.full and R.world == 1 and args.config == "C2" and not args.batch and not args.strong and not args.no_sweep:
         # where does the device saturate at one wave per SIMD?  The headline configuration at smaller batches (same generator, a few steps)
         sweep = []
         for nb in (1000, 10000):
@@ -908,15 +942,15 @@ def main():
 
     side = args.side_configs
     if side == "auto":
-        side = "C3,C4,C5" if (R.world == 1 and args.config == "C2" and not args.batch and not args.strong) else "none"
+        side = "C3,C4,C5" if (args.full and R.world == 1 and args.config == "C2" and not args.batch and not args.strong) else "none"
     side_steps = {"C3": (10, 2), "C4": (3, 1), "C5": (10, 2), "C2": (5, 1)}
     if side != "none":
         cfgs = {}
         for cfg in [s for s in side.split(",") if s and s != args.config]:
             st, wu = side_steps[cfg]
-            q, res, bm, info = R.run(cfg, st, wu, exact_steps=exact_steps[cfg] if want_exact else 0)
+            q, res, bm, info = R.run(cfg, st, wu, exact_steps=exact_steps[cfg] if want_exact else 0, probe_passes=args.full)
             if R.rank == 0:
-                r = R.report(cfg, q, res, info, st, sample(cfg), headline=False)
+                r = R.report(cfg, q, res, info, st, sample(cfg), headline=False, transfers=args.full)
                 cfgs[cfg] = {k: r[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "workload", "batch_per_gpu", "mean_iterations",
                                                "roofline", "checks", "arith", "exact", "transfers", "cpu_baseline", "parity_vs_cpu") if k in r}
             bm.close()

@@ -309,6 +309,41 @@ def test_kernel_resource_budgets():
         assert r["scratch"] <= scratch and r["occupancy"] >= occ, (name, r)
 
 
+def test_bench_dump_outputs_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: every array a caller of the timed path receives, float64; past the size cap the same seeded sample
+    of problems in every run, shards concatenated in order"""
+    import torch
+    import bench
+    n, m = 50, 150
+    per_qp = 8 * (n + m + 4)
+
+    def parts(N, shards=1):
+        g = torch.Generator().manual_seed(7)
+        out = []
+        for b in np.array_split(np.arange(N), shards):
+            k = len(b)
+            out.append(dict(x=torch.rand(k, n, generator=g, dtype=torch.float64), lam=torch.rand(k, m, generator=g, dtype=torch.float64),
+                            fval=torch.from_numpy(b.astype(np.float64)), soft_slack=torch.zeros(k, dtype=torch.float64),
+                            exitflag=torch.ones(k, dtype=torch.int32), iter=torch.arange(k, dtype=torch.int32)))
+        return out
+
+    small = parts(1000)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k in bench.DUMP_NAMES:
+        v = np.load(tmp_path / "small" / f"{k}.npy")
+        assert v.dtype == np.float64 and np.array_equal(v, small[0][k].numpy().astype(np.float64)), k
+    N = 100_000
+    for tag, shards in (("a", 1), ("b", 1), ("c", 3)):
+        bench.dump_outputs(str(tmp_path / tag), parts(N, shards))
+    total = sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in bench.DUMP_NAMES)
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "a" / "fval.npy")
+    assert len(idx) == bench.DUMP_BYTES // per_qp and np.all(np.diff(idx) > 0) and idx.max() < N
+    for k in bench.DUMP_NAMES:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")), k
+    assert np.array_equal(np.load(tmp_path / "c" / "fval.npy"), idx)      # three shards: the same problems picked
+
+
 def test_bench_gpus_flag_decides_the_ranks():
     """bench.py --gpus N: N > 1 without a launcher re-executes as N ranks under torch.distributed.run on the loopback interface;
     under a launcher the world size must be N; N == 1 stays in-process (tests/test_gpu_bench_contract.py runs all of it on the GPU)"""

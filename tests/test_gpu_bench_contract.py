@@ -69,7 +69,7 @@ def check_roofline(r, cfg):
 
 
 def test_bench_json_line(gpu_lib):
-    d = run_bench(["--steps", "2", "--warmup", "1", "--batch", "4096", "--cpu-sample", "512", "--side-configs", "C3,C5"])
+    d = run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "4096", "--cpu-sample", "512", "--side-configs", "C3,C5"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "configs"):
         assert k in d, k
@@ -117,7 +117,7 @@ def test_bench_json_line(gpu_lib):
 def test_bench_headline_carries_the_batch_sweep(gpu_lib):
     """the headline configuration at its own batch size also reports where the device saturates: C2 at 1 000 / 10 000 / 100 000 problems
     (`batch_sweep`), and -- when a counter pass of this build is committed -- the setup launch's own roofline record (`roofline.setup`)"""
-    d = run_bench(["--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--side-configs", "none", "--no-exact"])
+    d = run_bench(["--full", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--side-configs", "none", "--no-exact"])
     sw = d["batch_sweep"]
     assert [e["batch"] for e in sw] == [1000, 10000, 100000] and all(e["value"] > 0 and e["solve_ms"] > 0 for e in sw)
     assert sw[2]["value"] == d["value"] and sw[0]["value"] < sw[2]["value"]
@@ -127,6 +127,27 @@ def test_bench_headline_carries_the_batch_sweep(gpu_lib):
         assert st["bound"] == "hbm" and st["peak"] == 8000.0 and abs(st["frac"] - st["achieved"] / st["peak"]) < 1e-12
         assert abs(st["achieved"] - st["traffic"] / (st["avg_launch_ms"] * 1e-3) / 1e9) < 1e-6 * st["achieved"]
         assert st["traffic"] >= 0.9 * st["algorithmic_bytes_per_launch"] and "k_setup" in st["kernel"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(gpu_lib, tmp_path):
+    """without --full the run times the headline and nothing else (no side configs, CPU leg, sweep, exact mode, transfers);
+    --dump-outputs DIR writes what the last timed step returned, float64, and the same arguments give the same arrays every run"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        d = run_bench(["--steps", "3", "--warmup", "1", "--batch", "4096", "--dump-outputs", str(out)])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 4096 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        assert not any(k_ in d for k_ in ("configs", "cpu_baseline", "parity_vs_cpu", "batch_sweep", "exact", "transfers"))
+        assert d["checks"]["all_optimal"]
+        check_roofline(d["roofline"], "C2")
+        got = {name: np.load(out / f"{name}.npy") for name in ("x", "lam", "fval", "soft_slack", "exitflag", "iter")}
+        assert all(v.dtype == np.float64 for v in got.values())
+        assert got["x"].shape == (4096, 50) and got["lam"].shape == (4096, 150) and got["iter"].shape == (4096,)
+        assert (got["exitflag"] == 1).all() and abs(got["iter"].mean() - d["config"]["mean_iterations"]) < 1e-9
+        dumps.append(got)
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_bench_multi_entry_one_process(gpu_lib):
