@@ -67,6 +67,7 @@ EXPORTS = [
     "daqp_batch_solve_multi", "daqp_batch_setup_multi_shards", "daqp_batch_update_multi_shards", "daqp_batch_solve_multi_shards",
     "daqp_batch_device_bytes", "daqp_batch_rechecked", "daqp_batch_set_recheck", "daqp_batch_recheck_ms", "daqp_amd_last_error", "daqp_amd_device_count", "daqp_amd_version", "daqp_amd_has_tiny",
     "setup_daqp_ldp", "daqp_ldp", "ldp2qp_solution", "daqp_extract_result",
+    "daqp_minrep_batch", "daqp_minrep_batch_info", "daqp_batch_reset", "reset_daqp_workspace", "daqp_deactivate_constraints",
     "daqp_batch_enable_trace", "daqp_batch_read_trace", "daqp_batch_enable_profile", "daqp_batch_read_profile", "daqp_batch_read_ldp",
 ]
 
@@ -75,7 +76,7 @@ EXPORTS = [
 # object was compiled with other flags)
 UNITS = {
     "daqp_amd.hip": ["daqp_amd.hip", "kernels.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h", "setup_fast.hip.h", "prox.hip.h",
-                     "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h"],
+                     "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h"],
     "reg_kernel.hip": ["reg_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "reg32_kernel.hip": ["reg32_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "wg_kernel.hip": ["wg_kernel.hip", "wg_kernel.hip.h", "wg_ldp.hip.h", "wg_layout.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h"],
@@ -294,7 +295,15 @@ def lib():
     L.ldp2qp_solution.restype = None
     L.daqp_extract_result.argtypes = [C.POINTER(DAQPResult), vp]
     L.daqp_extract_result.restype = None
+    L.daqp_minrep.argtypes = [c_int_p, c_double_p, c_double_p, ci, ci, ci]
     L.daqp_minrep.restype = None
+    L.daqp_minrep_batch.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, C.POINTER(DAQPSettings), ci]
+    L.daqp_minrep_batch_info.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)]
+    L.daqp_batch_reset.argtypes = [vp]
+    L.reset_daqp_workspace.argtypes = [vp]
+    L.reset_daqp_workspace.restype = None
+    L.daqp_deactivate_constraints.argtypes = [vp]
+    L.daqp_deactivate_constraints.restype = None
     _lib = L
     return L
 

@@ -148,6 +148,14 @@ class Model:
         return x, res.fval, res.exitflag, {"solve_time": res.solve_time, "setup_time": 0.0, "iterations": res.iter,
                                            "nodes": res.nodes, "lam": lam}
 
+    def reset(self):
+        """daqp_deactivate_constraints + reset_daqp_workspace: the next solve starts from an empty working set on the LDP as it is."""
+        if self._ws is None:
+            raise RuntimeError("Model.reset called before setup")
+        lib().daqp_deactivate_constraints(self._ws)
+        lib().reset_daqp_workspace(self._ws)
+        return self
+
     def _free(self):
         if self._ws is not None:
             C.c_void_p.from_buffer(self._ws, 224).value = None  # borrowed settings are not ours to free
@@ -303,6 +311,14 @@ class BatchModel:
         self._out_keep = [o]
         return o
 
+    def reset(self):
+        """Every problem back to an empty working set (daqp_deactivate_constraints + reset_daqp_workspace per problem): the next
+        solve is a cold one on the LDPs as they are; an update(f, bounds) not yet applied stays pending."""
+        rc = lib().daqp_batch_reset(self._h)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_reset failed ({rc}): {_lib.last_error()}")
+        return self
+
     def set_primal_start(self, x):
         """api.c:636-641 for every problem: where the proximal iterations (singular H) start from; x: (N, n)."""
         keep = []
@@ -408,6 +424,54 @@ def solve_batch(H, f, A, bupper, blower=None, sense=None, ms=None, out="numpy", 
     finally:
         bm.close()
     return res
+
+
+def minrep_batch(A, b, ms=None, out="numpy", info=None, device=None, **settings):
+    """Redundant rows of P polyhedra {x : A[p] x <= b[p]} of one shape: A (P, m - ms, n), b (P, m) with the ms simple bounds
+    x_i <= b_i first; numpy arrays or torch device tensors (used in place).  Returns int32 (P, m): 1 redundant, 0 not, -1 a vanishing
+    row of A (not tested); out='torch' gives a device tensor.  All P * m row tests run as one batch on the GPU (daqp_minrep_batch in
+    include/daqp_amd.h: rows are normalised first, an empty polyhedron gives all ones).  info: a dict that receives 'unresolved',
+    the number of tests that ended with neither OPTIMAL nor INFEASIBLE (0 when every verdict is clean)."""
+    if b.ndim != 2:
+        raise ValueError("b must be (P, m)")
+    P, m = int(b.shape[0]), int(b.shape[1])
+    mA = 0 if A is None else int(A.shape[1])
+    if ms is None:
+        ms = m - mA
+    if A is not None and (A.ndim != 3 or int(A.shape[0]) != P or mA != m - ms):
+        raise ValueError("A must be (P, m - ms, n)")
+    n = int(A.shape[2]) if A is not None else ms      # (simple bounds only: the rows are the first ms coordinates)
+    keep = []
+    pa, mem_a = _ptr(A, np.float64, keep)
+    pb, mem_b = _ptr(b, np.float64, keep)
+    if mem_a is not None and mem_a != mem_b:
+        raise ValueError("mix of host and device arrays in one call")
+    st = default_settings(**settings)
+    if mem_b == MEM_DEVICE:
+        dev = keep[-1].device
+        red = torch.empty((P, m), dtype=torch.int32, device=dev)
+        pr = red.data_ptr()
+        device = dev.index if device is None else device
+        torch.cuda.current_stream(dev).synchronize()      # the library works on its own stream: the inputs must be there
+    else:
+        red = np.empty((P, m), np.int32)
+        pr = red.ctypes.data
+    rc = lib().daqp_minrep_batch(pr, pa, pb, P, n, m, ms, mem_b, C.byref(st), -1 if device is None else int(device))
+    if rc < 0:
+        raise RuntimeError(f"daqp_minrep_batch failed ({rc}): {_lib.last_error()}")
+    if info is not None:
+        info["unresolved"] = int(rc)
+    if out == "torch":
+        return red if _is_torch(red) else torch.from_numpy(red)
+    return red.cpu().numpy() if _is_torch(red) else red
+
+
+def minrep(A, b):
+    """daqp.pyx:636-652: redundant rows of {x : A x <= b}; ms = len(b) - A.shape[0] simple bounds come first in b.  int32 array of m."""
+    A, b = _np64(A), _np64(b)
+    A = A.reshape(-1, A.shape[-1]) if A.ndim >= 2 else A.reshape(0, b.size)
+    m, mA, n = b.size, A.shape[0], A.shape[1]
+    return minrep_batch(A[None] if mA else None, b[None], ms=m - mA)[0]
 
 
 def solve_batch_multi(H, f, A, bupper, blower=None, sense=None, ms=None, devices=None, **settings):

@@ -42,6 +42,8 @@ struct BatchDev {
     const DAQPSettings *st_dev;   // device copy of st (scalar-load friendly)
     int exact_setup;              // 1: M = A R^-1 in the reference's operation order (VALU); 0: MFMA f64
     int shared;                   // 1: one H, A for the whole batch (daqp_batch_setup_shared): Mblk, Rinv, scaling hold ONE problem's factors
+                                  // g > 1: groups of g consecutive problems share one set of factors (problem q reads those of group q / g;
+                                  // daqp_minrep_batch: g = m, the m row tests of a polyhedron); 0: every problem has its own
     DAQPSettings st;
     // regularising re-runs of k_setup (utils.c:356-377): only the problems flagged DAQP_NEEDS_SHIFT, with H + hshift[q] on the diagonal
     // (1), or the one setup pass of an LP batch (2): b.H is ONE identity matrix -- the reference's Rinv == RinvD == NULL
@@ -77,7 +79,13 @@ constexpr int kSetupOnlyMarked = 1 << 30;
 #define DAQP_PROX_SKIP (-101)
 
 __host__ __device__ inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-// index of problem q's factors (M, R^-1, scaling): its own, or the single shared set
-__device__ __forceinline__ size_t qf(const BatchDev &b, int q) { return b.shared ? (size_t)0 : (size_t)q; }
+// index of problem q's factors (M, R^-1, scaling): its own, the single shared set, or its group's (once per problem, in the prologue)
+__device__ __forceinline__ size_t qf(const BatchDev &b, int q)
+{
+    const int g = b.shared;
+    if (g == 0) return (size_t)q;
+    if (g == 1) return (size_t)0;
+    return (size_t)((unsigned)q / (unsigned)g);
+}
 
 } // namespace daqp_amd

@@ -26,6 +26,7 @@
 #include "wg_layout.hip.h"
 #include "tiny_setup.hip.h"
 #include "setup_blk.hip.h"
+#include "minrep.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -80,6 +81,8 @@ using namespace daqp_amd;
 namespace {
 
 thread_local char g_err[512] = "";
+thread_local float g_minrep_ms[2] = {0, 0};               // daqp_minrep_batch_info
+thread_local unsigned long long g_minrep_bytes = 0;
 void set_err(const char *fmt, ...)
 {
     va_list ap;
@@ -903,7 +906,13 @@ int daqp_amd_device_count(void)
 }
 void daqp_default_settings(DAQPSettings *settings) { default_settings(settings); }
 
+// group > 1: groups of `group` consecutive problems share one set of factors (Mblk, M32, R^-1, scaling are allocated per group: BatchDev::shared)
+static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, const DAQPSettings *settings, int device, int group);
 int daqp_batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, const DAQPSettings *settings, int device)
+{
+    return batch_create(out, N, n, m, ms, ns_max, settings, device, 0);
+}
+static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, const DAQPSettings *settings, int device, int group)
 {
     if (!out) return DAQP_EXIT_UNSUPPORTED;
     *out = nullptr;
@@ -927,7 +936,7 @@ int daqp_batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, 
     }
     if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
     const std::string env_key = env_signature();
-    if (N == 1 && pool_enabled()) {
+    if (N == 1 && group <= 1 && pool_enabled()) {
         DAQPBatch *hit = nullptr;
         {
             std::lock_guard<std::mutex> lk(g_pool_mu);
@@ -1094,11 +1103,12 @@ int daqp_batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, 
         return DAQP_EXIT_UNSUPPORTED;
     }
     const size_t Nn = (size_t)N;
+    const size_t Nf = group > 1 ? (size_t)((N + group - 1) / group) : Nn;      // sets of factors
     int rc = 0;
-    rc |= dev_alloc(b, &d.Mblk, Nn * d.nblk * d.npair * 128);
-    rc |= dev_alloc(b, &d.Rinv, Nn * d.rtri);
+    rc |= dev_alloc(b, &d.Mblk, Nf * d.nblk * d.npair * 128);
+    rc |= dev_alloc(b, &d.Rinv, Nf * d.rtri);
     rc |= dev_alloc(b, &d.v, Nn * n);
-    rc |= dev_alloc(b, &d.scaling, Nn * m);
+    rc |= dev_alloc(b, &d.scaling, Nf * m);
     rc |= dev_alloc(b, &d.dupper, Nn * m);
     rc |= dev_alloc(b, &d.dlower, Nn * m);
     rc |= dev_alloc(b, &d.sense, Nn * m);
@@ -1114,14 +1124,15 @@ int daqp_batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, 
         if (b->img_rows_warm - b->img_cache_warm > t2) t2 = b->img_rows_warm - b->img_cache_warm;
         if (t2 > 0) rc |= dev_alloc(b, &d.rowc_g, Nn * (size_t)(t2 * d.ldrc));
     }
-    if (b->setup_spill || b->fact_gs) rc |= dev_alloc(b, &d.setup_g, Nn * 2 * (size_t)round_up(d.rtri, 2));
+    // (a grouped batch is never set up from H / A: the scratch of the QP setup kernels stays away)
+    if ((b->setup_spill || b->fact_gs) && group <= 1) rc |= dev_alloc(b, &d.setup_g, Nn * 2 * (size_t)round_up(d.rtri, 2));
     // fp32 image of M for the workgroup kernel's screening scan (generic setup kernel only: it is the one that writes it)
     if (b->use_wg && !b->fast_setup && !getenv("DAQP_AMD_NO_SCAN32")) {
-        const size_t cnt = Nn * (size_t)d.nblk * d.nquad * 256;
+        const size_t cnt = Nf * (size_t)d.nblk * d.nquad * 256;
         rc |= dev_alloc(b, &d.M32, cnt);
         if (!rc) HIPCHK(hipMemset(d.M32, 0, cnt * sizeof(float)));
     }
-    if (!b->fast_setup) {   // zeroed once: the kernel only ever writes the upper triangle
+    if (!b->fast_setup && group <= 1) {   // zeroed once: the kernel only ever writes the upper triangle
         const size_t sq = Nn * (size_t)round_up(n, 32) * (size_t)round_up(n, 16);
         rc |= dev_alloc(b, &d.setup_sq, sq);
         if (!rc) HIPCHK(hipMemset(d.setup_sq, 0, sq * sizeof(double)));
@@ -1229,7 +1240,7 @@ int daqp_batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, 
     d.st_dev = b->st_dev;
     if (rc) { daqp_batch_free(b); return DAQP_EXIT_UNSUPPORTED; }
     // padding rows/columns of the blocked M image are never written by the kernels: keep them defined
-    if (hipMemset(d.Mblk, 0, Nn * d.nblk * d.npair * 128 * sizeof(double)) != hipSuccess ||
+    if (hipMemset(d.Mblk, 0, Nf * d.nblk * d.npair * 128 * sizeof(double)) != hipSuccess ||
         hipMemset(d.vecs, 0, Nn * 5 * cap * sizeof(double)) != hipSuccess ||
         hipMemset(d.qs, 0, Nn * sizeof(QState)) != hipSuccess) {
         set_err("hipMemset failed");
@@ -2478,13 +2489,121 @@ int daqp_first_violating(c_float *x, c_float *A, c_float *bu, c_float *bl, int n
     }
     return m;
 }
-// api.h: daqp_minrep (redundancy removal built on repeated LDP solves, src/api.c) is outside this path.  The symbol exists
-// so that the reference's Cython module (daqp.pxd:65) links against this library; it leaves is_redundant untouched and
-// records the reason in daqp_amd_last_error().
+// ------------------------------------------------------------------------------------
+// redundancy removal (api.c:531-558, utils.c:808-835) and the reset of a kept workspace (daqp.c:142-146, auxiliary.c:482-497)
+// ------------------------------------------------------------------------------------
+// P polyhedra {x : A x <= b} of one shape: A is P*(m-ms)*n row-major, b is P*m with the simple bounds x_i <= b_i first, is_redundant
+// is P*m (1: redundant, 0: not, -1: a vanishing row of A, not tested).  Every row is tested on its own -- one LDP on M = A with the
+// row pinned as an equality, INFEASIBLE meaning redundant --, all P*m tests in one batch whose m problems per polyhedron share one
+// image of M (minrep.hip.h).  Returns the number of tests that ended with a flag other than OPTIMAL / INFEASIBLE (0 when every
+// verdict is clean; such tests are reported as not redundant), or a negative exit flag.
+int daqp_minrep_batch(int *is_redundant, const c_float *A, const c_float *rhs, int P, int n, int m, int ms, int memory, const DAQPSettings *settings, int device)
+{
+    if (!is_redundant || !rhs || P <= 0 || n <= 0 || m <= 0 || ms < 0 || ms > m || ms > n || (m > ms && !A)) {
+        set_err("daqp_minrep_batch: bad arguments P=%d n=%d m=%d ms=%d", P, n, m, ms);
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if ((long long)P * m > 0x7fffffffLL / 4) { set_err("daqp_minrep_batch: P * m = %lld row tests exceed one batch", (long long)P * m); return DAQP_EXIT_UNSUPPORTED; }
+    const int N = P * m;
+    DAQPBatch *b = nullptr;
+    int rc = batch_create(&b, N, n, m, ms, 0, settings, device, m);
+    if (rc) return rc;
+    BatchDev &d = b->d;
+    int *dev_out = nullptr, *other = nullptr;
+    const double *dA = nullptr, *db = nullptr;
+    auto run = [&]() -> int {
+        HIPCHK(hipSetDevice(b->device));
+        if (stage(b, A, memory, (size_t)P * d.mA * n, &b->sA, &b->nA, &dA) || stage(b, rhs, memory, (size_t)N, &b->sbu, &b->nbu, &db)) return DAQP_EXIT_UNSUPPORTED;
+        if (dev_alloc(b, &b->structural, (size_t)N) || dev_alloc(b, &other, 1)) return DAQP_EXIT_UNSUPPORTED;
+        if (memory == DAQP_MEM_DEVICE) dev_out = is_redundant;
+        else if (dev_alloc(b, &dev_out, (size_t)N)) return DAQP_EXIT_UNSUPPORTED;
+        HIPCHK(hipMemsetAsync(other, 0, sizeof(int), b->stream));
+        d.shared = m > 1 ? m : 0;
+        d.H = nullptr; d.f = nullptr; d.A = dA; d.bu = db; d.bl = nullptr; d.sense_in = nullptr;
+        b->was_shared = true;      // (one image of M per polyhedron: nothing per problem that daqp_batch_update could re-form)
+        b->pending_mask = 0; b->part_mask = 0; b->n_prox_qps = 0; b->reg_pending = false; b->exact_sticky = false;
+        b->fresh = false;          // no second pass (recheck.hip.h re-runs a QP setup from H / A, which do not exist here)
+        HIPCHK(hipEventRecord(b->ev[0], b->stream));
+        hipLaunchKernelGGL(k_minrep_setup, dim3(P), dim3(256), 0, b->stream, d, dA, b->structural);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_minrep_init, dim3(N), dim3(64), 0, b->stream, d, db, (const int *)b->structural);
+        HIPCHK(hipGetLastError());
+        b->is_setup = true;
+        int r2 = launch_ldp(b, 1);      // the pinned row enters the working set (utils.c:817-818)
+        if (r2) return r2;
+        HIPCHK(hipEventRecord(b->ev[1], b->stream));
+        b->timed_setup = true;
+        DAQPBatchResult res;
+        memset(&res, 0, sizeof(res));
+        res.memory = DAQP_MEM_DEVICE;   // results stay in the batch's own buffers: only the flags are looked at
+        r2 = daqp_batch_solve(b, &res);
+        if (r2) return r2;
+        hipLaunchKernelGGL(k_minrep_verdict, dim3((N + 255) / 256), dim3(256), 0, b->stream, N, m, (const int *)b->oflag, (const int *)b->structural, dev_out, other);
+        HIPCHK(hipGetLastError());
+        int n_other = 0;
+        if (memory != DAQP_MEM_DEVICE) HIPCHK(hipMemcpyAsync(is_redundant, dev_out, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(&n_other, other, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (n_other > 0) set_err("daqp_minrep_batch: %d of %d row tests ended with neither OPTIMAL nor INFEASIBLE (reported as not redundant)", n_other, N);
+        return n_other;
+    };
+    rc = run();
+    if (const char *e = getenv("DAQP_AMD_MINREP_TIMES")) {      // tools/minrep_bench.py: setup and solve launches of the last call, from the batch's events
+        float t_setup = 0, t_solve = 0;
+        if (atoi(e) != 0 && rc >= 0 && daqp_batch_kernel_ms(b, &t_setup, &t_solve) == 0) { g_minrep_ms[0] = t_setup; g_minrep_ms[1] = t_solve; }
+    }
+    g_minrep_bytes = daqp_batch_device_bytes(b);
+    daqp_batch_free(b);
+    return rc;
+}
+// setup / solve launches (ms, HIP events) of this thread's last daqp_minrep_batch when DAQP_AMD_MINREP_TIMES=1, and its device memory
+int daqp_minrep_batch_info(float *setup_ms, float *solve_ms, unsigned long long *device_bytes)
+{
+    if (setup_ms) *setup_ms = g_minrep_ms[0];
+    if (solve_ms) *solve_ms = g_minrep_ms[1];
+    if (device_bytes) *device_bytes = g_minrep_bytes;
+    return 0;
+}
+
+// api.h: the reference's signature -- one polyhedron from host memory, default settings, the current device.  Without a device, or
+// for a shape the batch path cannot take, is_redundant is filled with -1 and daqp_amd_last_error() says why (there is no CPU path).
 void daqp_minrep(int *is_redundant, c_float *A, c_float *b, int n, int m, int ms)
 {
-    (void)is_redundant; (void)A; (void)b; (void)n; (void)m; (void)ms;
-    set_err("daqp_minrep is outside the dense-QP path of this library");
+    if (!is_redundant || m <= 0) { set_err("daqp_minrep: bad arguments"); return; }
+    const int rc = daqp_minrep_batch(is_redundant, A, b, 1, n, m, ms, DAQP_MEM_HOST, nullptr, -1);
+    if (rc < 0) for (int i = 0; i < m; ++i) is_redundant[i] = -1;
+}
+
+// daqp_deactivate_constraints + reset_daqp_workspace for every problem of a batch: the next daqp_batch_solve starts from an empty working
+// set on the LDP as it stands (a daqp_batch_update(UPDATE_v|UPDATE_d) that the next solve launch still owes stays owed)
+static int batch_reset(DAQPBatch *b, int what)
+{
+    if (!b) return DAQP_EXIT_UNSUPPORTED;
+    if (!b->is_setup) { set_err("reset before daqp_batch_setup"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(b->device));
+    if (resolve_setup(b)) return DAQP_EXIT_UNSUPPORTED;
+    hipLaunchKernelGGL(k_reset, dim3(b->d.N), dim3(64), 0, b->stream, b->d, what);
+    HIPCHK(hipGetLastError());
+    b->one_valid = false;
+    if (b->img_ho_pin) *b->img_ho_pin = 0;      // (hand-over statistics of warm launches say nothing about cold ones)
+    return 0;
+}
+int daqp_batch_reset(DAQPBatch *b) { return batch_reset(b, kResetDeactivate | kResetWorkspace); }
+// daqp.c:142-146
+void reset_daqp_workspace(DAQPWorkspace *work)
+{
+    if (!work) return;
+    DAQPBatch *b = ws_batch(work);
+    if (!b) { work->sing_ind = DAQP_EMPTY_IND; work->n_active = 0; work->reuse_ind = 0; work->iterations = 0; return; }
+    if (batch_reset(b, kResetWorkspace) == 0) refresh_mirrors(work);
+}
+// auxiliary.c:482-497; here the working set goes with the bits (n_active = 0), so that the two calls may come in either order
+void daqp_deactivate_constraints(DAQPWorkspace *work)
+{
+    if (!work) return;
+    DAQPBatch *b = ws_batch(work);
+    if (!b) return;
+    if (batch_reset(b, kResetDeactivate) == 0) refresh_mirrors(work);
 }
 
 } // extern "C"

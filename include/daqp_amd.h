@@ -158,7 +158,31 @@ void daqp_set_primal_start(DAQPWorkspace *work, c_float *x);                   /
 void allocate_daqp_workspace(DAQPWorkspace *work, int n, int ns);                /* api.h:41 (records n; state is created by setup_daqp) */
 void allocate_daqp_ldp(DAQPWorkspace *work, int n, int m, int ms, int alloc_R, int alloc_v);   /* api.h:42 (records n, m, ms) */
 int daqp_first_violating(c_float *x, c_float *A, c_float *bu, c_float *bl, int n, int m, int ms, c_float tol);   /* api.c:562-574, host-only */
-void daqp_minrep(int *is_redundant, c_float *A, c_float *b, int n, int m, int ms); /* api.h:55: outside the path (link stub: is_redundant untouched, daqp_amd_last_error() says so) */
+/* api.h:55, api.c:531-558: which rows of {x : A x <= b} are redundant (is_redundant[i] = 1) -- b holds the ms simple bounds x_i <= b_i first,
+ * A the m - ms general rows.  One polyhedron from host memory through daqp_minrep_batch below (default settings, the current device); without
+ * a device, or for a shape daqp_batch_create cannot take (working sets of up to n + 1 rows), is_redundant is filled with -1 and
+ * daqp_amd_last_error() says why.  There is no CPU path. */
+void daqp_minrep(int *is_redundant, c_float *A, c_float *b, int n, int m, int ms);
+/* P polyhedra of one shape at once: A is P*(m-ms)*n row-major, b is P*m, is_redundant is P*m; `memory` (DAQP_MEM_HOST / DAQP_MEM_DEVICE) applies to
+ * all three arrays, device arrays are used in place.  Every row is tested on its own (one LDP with the row pinned as an equality; INFEASIBLE means
+ * the face is empty, the row redundant), all P*m tests as ONE batch whose m problems per polyhedron read one image of A.  Differences from
+ * the reference's sequential loop (utils.c:808-835), all documented in DESIGN.md:
+ *  - rows of A are normalised to unit length first (as the QP setup does), so settings->primal_tol is compared with the NORMALISED slack;
+ *    verdicts agree with the reference's wherever the redundancy margin is clear of the tolerance;
+ *  - an EMPTY polyhedron gives all ones (the reference's answer there depends on the order of the rows): all ones = the polyhedron is empty;
+ *  - a vanishing row of A (|A_i|^2 < zero_tol) takes no part and is reported as -1.
+ * Returns the number of row tests that ended with a flag other than OPTIMAL / INFEASIBLE (iteration limit, cycling: reported as not redundant,
+ * daqp_amd_last_error() names the count) -- 0 when every verdict is clean -- or a negative exit flag.
+ * Device memory: per row test the iterate of an ordinary problem of that shape plus its own d (2 m doubles) and sense; per polyhedron one image of A. */
+int daqp_minrep_batch(int *is_redundant, const c_float *A, const c_float *b, int P, int n, int m, int ms, int memory, const DAQPSettings *settings, int device);
+/* this thread's last daqp_minrep_batch: device bytes it held, and (environment DAQP_AMD_MINREP_TIMES=1) its setup / solve launches in ms from HIP events */
+int daqp_minrep_batch_info(float *setup_ms, float *solve_ms, unsigned long long *device_bytes);
+/* daqp.c:142-146: sing_ind = EMPTY, reuse_ind = 0, n_active = 0, iterations = 0 -- on the device state of a kept workspace and its host mirrors */
+void reset_daqp_workspace(DAQPWorkspace *work);
+/* auxiliary.c:482-497: the ACTIVE bit of every working-set row that is not IMMUTABLE is cleared; here the working set is emptied with it
+ * (n_active = 0; the stored factor and multipliers count as empty), so the two calls may come in either order.  The next daqp_solve starts
+ * cold on the LDP as it stands. */
+void daqp_deactivate_constraints(DAQPWorkspace *work);
 int setup_daqp_ldp(DAQPWorkspace *work, DAQPProblem *qp, const int init_mask);      /* api.c:161-209 (api.h:35) */
 int daqp_ldp(DAQPWorkspace *work);                                                  /* daqp.c:6-108 (daqp.h:12): iterate from the workspace's state; returns the exit flag */
 void ldp2qp_solution(DAQPWorkspace *work);                                          /* daqp.c:111-139 (daqp.h:13): done on the device by daqp_ldp -- a no-op kept for callers of the pair */
@@ -257,6 +281,9 @@ int daqp_batch_prox_info(DAQPBatch *b, int *n_prox_host, int *outer_host, c_floa
 int daqp_batch_setup_flags(DAQPBatch *b, int *flags_host);
 /* copy out working sets: n_active (host int[N]) and WS (host int[N*(n+ns_max+1)], -1 padded); either may be NULL */
 int daqp_batch_working_sets(DAQPBatch *b, int *n_active_host, int *ws_host);
+/* daqp_deactivate_constraints + reset_daqp_workspace for every problem of the batch: the next daqp_batch_solve starts from empty working sets
+ * (a daqp_batch_update(UPDATE_v|UPDATE_d) that the next solve launch still owes stays owed) */
+int daqp_batch_reset(DAQPBatch *b);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 
