@@ -8,4 +8,15 @@ from ._lib import build, default_settings, last_error, lib, LIBPATH  # noqa: F40
 from .api import (BatchModel, MultiBatchModel, Model, minrep, minrep_batch, solve, solve_batch, solve_batch_multi, UPDATE_Rinv, UPDATE_M, UPDATE_v, UPDATE_d,  # noqa: F401
                   UPDATE_sense, UPDATE_unconstrained, UPDATE_eliminate)
 
-__all__ = ["build", "lib", "solve", "Model", "solve_batch", "solve_batch_multi", "minrep", "minrep_batch", "BatchModel", "MultiBatchModel", "default_settings", "last_error"]
+
+
+def __getattr__(name):
+    # the autograd layer needs torch: imported on first use, so that the package works on numpy without it
+    if name in ("layer", "qp_layer"):
+        import importlib
+        mod = importlib.import_module(".layer", __name__)
+        return mod if name == "layer" else mod.qp_layer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["qp_layer", "build", "lib", "solve", "Model", "solve_batch", "solve_batch_multi", "minrep", "minrep_batch", "BatchModel", "MultiBatchModel", "default_settings", "last_error"]

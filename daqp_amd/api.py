@@ -311,6 +311,39 @@ class BatchModel:
         self._out_keep = [o]
         return o
 
+    def backward(self, grad_x, out="torch"):
+        """The adjoint of the last solve (daqp_batch_backward, include/daqp_amd.h): for grad_x = dl/dx of shape (N, n) returns
+        dict(dz, dbupper, dblower, status) with dl/df = -dz, dl/dH = -1/2 (dz x' + x dz'), dl/dA_i = -(lam_i dz + dnu_i x)' on the
+        general rows of the working set (dnu = dbupper + dblower), dl/dbupper = dbupper, dl/dblower = dblower.  status (N,) int32:
+        0, or why that problem has no derivative (its outputs are zero then).  out='torch': device tensors, grad_x a device tensor,
+        nothing waits for the device; out='numpy': host arrays.  Raises unless the last operation on the batch was a successful
+        solve(), and for batches with soft constraints (ns_max > 0)."""
+        N, n, m = self.N, self.n, self.m
+        keep = []
+        if out == "torch":
+            dev = torch.device("cuda", self.device)
+            g = torch.as_tensor(grad_x, dtype=torch.float64, device=dev).contiguous()
+            if tuple(g.shape) != (N, n):
+                raise ValueError(f"grad_x must have shape {(N, n)}")
+            keep.append(g)
+            o = dict(dz=torch.empty((N, n), dtype=torch.float64, device=dev), dbupper=torch.empty((N, m), dtype=torch.float64, device=dev),
+                     dblower=torch.empty((N, m), dtype=torch.float64, device=dev), status=torch.empty(N, dtype=torch.int32, device=dev))
+            ptrs = [g.data_ptr()] + [o[k].data_ptr() for k in ("dz", "dbupper", "dblower", "status")]
+            mem = MEM_DEVICE
+        else:
+            g = grad_x.detach().cpu().numpy() if _is_torch(grad_x) else grad_x
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if g.shape != (N, n):
+                raise ValueError(f"grad_x must have shape {(N, n)}")
+            o = dict(dz=np.empty((N, n)), dbupper=np.empty((N, m)), dblower=np.empty((N, m)), status=np.empty(N, np.int32))
+            ptrs = [g.ctypes.data] + [o[k].ctypes.data for k in ("dz", "dbupper", "dblower", "status")]
+            mem = MEM_HOST
+        rc = lib().daqp_batch_backward(self._h, *ptrs, mem)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_backward failed ({rc}): {_lib.last_error()}")
+        self._bw_keep = [keep, o]      # the launch reads / writes them after this call has returned
+        return o
+
     def reset(self):
         """Every problem back to an empty working set (daqp_deactivate_constraints + reset_daqp_workspace per problem): the next
         solve is a cold one on the LDPs as they are; an update(f, bounds) not yet applied stays pending."""

@@ -27,6 +27,7 @@
 #include "tiny_setup.hip.h"
 #include "setup_blk.hip.h"
 #include "minrep.hip.h"
+#include "backward.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -74,6 +75,10 @@ extern template __global__ void k_ldp_wg<2, false>(BatchDev, int);
 extern template __global__ void k_ldp_wg<2, true>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, false>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, true>(BatchDev, int);
+// the adjoint kernel: backward_kernel.hip
+extern template __global__ void k_backward<64, true, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, false>(BatchDev, BackwardArgs);
 }
 
 using namespace daqp_amd;
@@ -227,6 +232,12 @@ struct DAQPBatch {
     DAQPBatch *redo = nullptr; // companion batch in the exact mode (created with the first infeasible verdict, grown on demand)
     int *redo_list = nullptr, *redo_count = nullptr, *pin_redo = nullptr, *pin_redo_dev = nullptr;   // pin_redo: a mapped host word the marking kernel writes
     int rechecked = 0;         // problems the last solve sent through the second pass
+    // daqp_batch_backward (backward.hip.h)
+    bool solved = false;       // the last operation on the batch was a successful daqp_batch_solve: the stored iterate is that of the reported optimum
+    double *bw_scratch = nullptr;   // [bw_grid][backward_scratch_doubles]: rows and Gram matrix of shapes that LDS does not hold
+    int bw_grid = 0;
+    double *bw_g = nullptr, *bw_dz = nullptr, *bw_dbu = nullptr, *bw_dbl = nullptr;   // staging of host-resident arguments
+    int *bw_status = nullptr;
 };
 
 namespace {
@@ -957,6 +968,7 @@ static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max
             if (put_async(hit->st_dev, hd.st, hit->stream) ||
                 hipMemsetAsync(hd.vecs, 0, (size_t)5 * hd.cap * sizeof(double), hit->stream) != hipSuccess ||
                 hipMemsetAsync(hd.qs, 0, sizeof(QState), hit->stream) != hipSuccess) { destroy_batch(hit); set_err("reset of a pooled workspace failed"); return DAQP_EXIT_UNSUPPORTED; }
+            hit->solved = false;
             *out = hit;
             return 0;
         }
@@ -1425,6 +1437,7 @@ int batch_setup(DAQPBatch *b, const DAQPBatchProblem *p, int init_mask, bool fre
         return DAQP_EXIT_UNSUPPORTED;
     }
     const bool lp = p->H == nullptr || (b->ident && p->H == b->ident);   // api.c:183-185
+    b->solved = false;
     b->pending_mask = 0;   // a full setup supersedes any deferred update
     b->part_mask = 0;
     b->exact_sticky = false;
@@ -1574,6 +1587,7 @@ int daqp_batch_setup_shared(DAQPBatch *b, const DAQPBatchProblem *p, int init_ma
         return DAQP_EXIT_UNSUPPORTED;
     }
     (void)init_mask;   // the unconstrained shortcut / elimination are per-problem decisions of daqp_quadprog: not taken here
+    b->solved = false;
     b->pending_mask = 0;
     b->part_mask = 0;
     b->n_prox_qps = 0;
@@ -1705,6 +1719,7 @@ int daqp_batch_update(DAQPBatch *b, int mask, const DAQPBatchProblem *p)
     int rc = check_problem(b, p);
     if (rc) return rc;
     if (!b->is_setup) { set_err("daqp_batch_update before daqp_batch_setup"); return DAQP_EXIT_UNSUPPORTED; }
+    b->solved = false;
     HIPCHK(hipSetDevice(b->device));
     if (resolve_setup(b)) return DAQP_EXIT_UNSUPPORTED;
     b->fresh = false;
@@ -1821,6 +1836,7 @@ int daqp_batch_solve(DAQPBatch *b, DAQPBatchResult *r)
 {
     if (!b || !r) { set_err("null batch or result"); return DAQP_EXIT_UNSUPPORTED; }
     if (!b->is_setup) { set_err("daqp_batch_solve before daqp_batch_setup"); return DAQP_EXIT_UNSUPPORTED; }
+    b->solved = false;
     HIPCHK(hipSetDevice(b->device));
     BatchDev &d = b->d;
     const bool dev = r->memory == DAQP_MEM_DEVICE;
@@ -1865,6 +1881,7 @@ int daqp_batch_solve(DAQPBatch *b, DAQPBatchResult *r)
     b->fresh = false;
     HIPCHK(hipEventRecord(b->ev[3], b->stream));
     b->timed_solve = true;
+    b->solved = true;      // (a copy-out that fails below returns nonzero: the caller has no results, and a later backward would have none to go with)
     if (!dev && d.N == 1 && b->pin_out != nullptr) {   // one problem: the result slab, mapped (the kernels wrote it in place) or in one copy
         if (b->defer_wait) return 0;                    // (daqp_ldp: more work goes behind this, one wait for all of it, then collect_one)
         rc = collect_one(b, r);
@@ -1955,6 +1972,63 @@ int daqp_batch_working_sets(DAQPBatch *b, int *n_active_host, int *ws_host)
         for (int i = 0; i < b->d.N; ++i) n_active_host[i] = qs[i].n_active;
     }
     if (ws_host) HIPCHK(hipMemcpy(ws_host, b->d.WS, sizeof(int) * (size_t)b->d.N * b->d.cap, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The adjoint of the last solve (include/daqp_amd.h, backward.hip.h): one launch on the batch's stream.  Refusals come before any
+// device work.  Host-resident arguments go through the batch's own staging buffers and the call waits for the results; device-resident
+// ones are used in place and nothing waits.
+int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory)
+{
+    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported"); return DAQP_EXIT_UNSUPPORTED; }
+    if (!b->is_setup || !b->solved || b->pending_mask) {
+        set_err("daqp_batch_backward: the last operation on the batch was not a successful daqp_batch_solve");
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    const BatchDev &d = b->d;
+    const size_t N = d.N, n = d.n, m = d.m;
+    // ---- which instantiation: one wavefront with everything in LDS (n <= 64), a workgroup with rows + Gram matrix in LDS, or in scratch
+    const bool small = d.n <= 64;
+    const size_t lds_nl = backward_lds_bytes(d.n, d.cap, small, true);
+    const bool nl = small || lds_nl <= (size_t)144 * 1024;
+    const size_t lds = nl ? lds_nl : backward_lds_bytes(d.n, d.cap, false, false);
+    void (*kb)(BatchDev, BackwardArgs) = small ? k_backward<64, true, true> : (nl ? k_backward<256, false, true> : k_backward<256, false, false>);
+    BackwardArgs a{};
+    int grid = d.N;
+    if (!nl) {
+        a.scratch_per_wg = backward_scratch_doubles(d.n, d.cap);
+        if (!b->bw_scratch) {
+            // persistent workgroups, at most 512 of them and at most 256 MiB of scratch
+            size_t g = ((size_t)256 << 20) / (a.scratch_per_wg * sizeof(double));
+            if (g > 512) g = 512;
+            if (g < 16) g = 16;
+            if (g > N) g = N;
+            if (dev_alloc(b, &b->bw_scratch, g * a.scratch_per_wg)) return DAQP_EXIT_UNSUPPORTED;
+            b->bw_grid = (int)g;
+        }
+        a.scratch = b->bw_scratch;
+        grid = b->bw_grid;
+    }
+    if (memory == DAQP_MEM_DEVICE) { a.grad_x = grad_x; a.dz = dz; a.dbupper = dbupper; a.dblower = dblower; a.status = status; }
+    else {
+        if (!b->bw_status && (dev_alloc(b, &b->bw_g, N * n) || dev_alloc(b, &b->bw_dz, N * n) || dev_alloc(b, &b->bw_dbu, N * m) ||
+                         dev_alloc(b, &b->bw_dbl, N * m) || dev_alloc(b, &b->bw_status, N)))
+            return DAQP_EXIT_UNSUPPORTED;
+        HIPCHK(hipMemcpyAsync(b->bw_g, grad_x, N * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        a.grad_x = b->bw_g; a.dz = b->bw_dz; a.dbupper = b->bw_dbu; a.dblower = b->bw_dbl; a.status = b->bw_status;
+    }
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kb, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
+    HIPCHK(hipGetLastError());
+    if (memory != DAQP_MEM_DEVICE) {
+        HIPCHK(hipMemcpyAsync(dz, b->bw_dz, N * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (m) HIPCHK(hipMemcpyAsync(dbupper, b->bw_dbu, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (m) HIPCHK(hipMemcpyAsync(dblower, b->bw_dbl, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(status, b->bw_status, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
     return 0;
 }
 
@@ -2582,6 +2656,7 @@ static int batch_reset(DAQPBatch *b, int what)
     if (!b->is_setup) { set_err("reset before daqp_batch_setup"); return DAQP_EXIT_UNSUPPORTED; }
     HIPCHK(hipSetDevice(b->device));
     if (resolve_setup(b)) return DAQP_EXIT_UNSUPPORTED;
+    b->solved = false;
     hipLaunchKernelGGL(k_reset, dim3(b->d.N), dim3(64), 0, b->stream, b->d, what);
     HIPCHK(hipGetLastError());
     b->one_valid = false;

@@ -46,6 +46,9 @@ typedef double c_float; /* the path computes in fp64 only (reference types.h:8-1
 #define DAQP_EXIT_OVERDETERMINED_INITIAL -6
 #define DAQP_EXIT_TIMELIMIT -7
 #define DAQP_EXIT_UNSUPPORTED -8
+/* per-problem status of daqp_batch_backward only (never an exit flag of a solve): the Gram matrix of the active rows is numerically
+   singular (a pivot of its Cholesky factor below settings->zero_tol) -- linearly dependent active constraints, no unique adjoint */
+#define DAQP_BACKWARD_SINGULAR -20
 
 /* ---- daqp_update_ldp masks (reference include/constants.h:54-61) ---- */
 #define DAQP_UPDATE_Rinv 1
@@ -284,6 +287,36 @@ int daqp_batch_working_sets(DAQPBatch *b, int *n_active_host, int *ws_host);
 /* daqp_deactivate_constraints + reset_daqp_workspace for every problem of the batch: the next daqp_batch_solve starts from empty working sets
  * (a daqp_batch_update(UPDATE_v|UPDATE_d) that the next solve launch still owes stays owed) */
 int daqp_batch_reset(DAQPBatch *b);
+/* Derivative of the solutions of the last daqp_batch_solve: the adjoint (backward) pass of implicit differentiation.
+ * With C = [first ms rows of I; A], W the rows of the stored working set, C_W those rows (unsigned) and lam the signed multipliers
+ * the solve returned, the optimum satisfies  H x + f + C_W' lam_W = 0,  C_W x = b_W.  For an upstream gradient g = dl/dx per
+ * problem (grad_x: N*n) the call solves
+ *
+ *        [ H    C_W' ] [ dz  ]   [ g ]
+ *        [ C_W  0    ] [ dnu ] = [ 0 ]
+ *
+ * on the kept factor of H (nothing is factored again but the n_active x n_active Gram matrix of the active rows) and returns
+ *   dz       N*n   the caller forms   dl/df = -dz,   dl/dH = -1/2 (dz x' + x dz'),
+ *                                     dl/dA_i = -(lam_i dz + dnu_i x)' for the general rows i in W, zero for every other row
+ *   dbupper  N*m   dl/dbupper: dnu_i for the rows of W held at their upper bound, zero elsewhere
+ *   dblower  N*m   dl/dblower: dnu_i for the rows of W held at their lower bound, zero elsewhere
+ *                  (every dnu_i goes to exactly one of the two; an equality row, bupper == blower, may appear on either side;
+ *                   dnu = dbupper + dblower)
+ *   status   N     0: done.  The problem's exit flag when its solve (or setup / update) did not end DAQP_EXIT_OPTIMAL;
+ *                  DAQP_EXIT_UNSUPPORTED when it went through the proximal loop (singular H, LP); DAQP_BACKWARD_SINGULAR when
+ *                  the active rows are linearly dependent.  All three outputs of such a problem are zero.
+ * x and lam are those of the solve, in the caller's units like everything here.  A problem that took the unconstrained shortcut
+ * has W empty: dz = H^-1 g.  A batch set up with shared H and A is supported; the outputs are per problem (dl/dH and dl/dA of
+ * the shared matrices are the sums over the batch).
+ * `memory` (DAQP_MEM_HOST / DAQP_MEM_DEVICE) applies to all five arrays.  The call runs on the batch's stream; with device memory
+ * it only enqueues (no host synchronisation), with host memory it returns when the results are there.
+ * Returns nonzero, with the reason in the last-error string and without any device work, when
+ *   - the last operation on the batch was not a successful daqp_batch_solve (a setup, update or reset since then invalidates
+ *     the stored optimum),
+ *   - the batch was created with ns_max > 0: SOFT CONSTRAINTS ARE OUT OF SCOPE (they change the (2,2) block of the system),
+ *   - a pointer is NULL.
+ * Not differentiated: lam, fval. */
+int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 

@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Time of BatchModel.backward next to the forward step it follows, at the two headline shapes of BASELINE.md.
+
+  python tools/bench_backward.py [--configs C2,C3] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
+
+Per shape: N device-resident QPs (daqp_amd.synthetic.generate_batch_torch), forward = BatchModel.setup + solve with device outputs,
+backward = one BatchModel.backward on a device-resident grad_x; both timed with HIP events around K calls after W warm-up calls
+(device time, the stream drained before and after).  One JSON line per shape is printed and appended to --out."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = {"C2": (50, 150, 0, 20, 20_000), "C3": (12, 48, 0, 5, 100_000)}     # n, m, ms, n_active, default batch
+
+
+def timed(fn, steps, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="C2,C3")
+    ap.add_argument("--batch", type=int, default=0)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join("profiles", "backward_bench.jsonl"))
+    a = ap.parse_args()
+    import torch
+    import daqp_amd
+    from daqp_amd.synthetic import generate_batch_torch
+    for cfg in a.configs.split(","):
+        n, m, ms, nact, N = SHAPES[cfg]
+        N = a.batch or N
+        q = generate_batch_torch(N, n, m, ms, nact, seed=1)
+        bm = daqp_amd.BatchModel(N, n, m, ms)
+
+        def forward():
+            bm.setup(q["H"], q["f"], q["A"], q["bupper"], q["blower"])
+            return bm.solve(out="torch")
+
+        r = forward()
+        g = torch.randn(N, n, dtype=torch.float64, device="cuda")
+        o = bm.backward(g)
+        ok = int((o["status"] == 0).sum())
+        fwd_ms = timed(forward, a.steps, a.warmup)
+        setup_ms, solve_ms = bm.kernel_ms()
+        bwd_ms = timed(lambda: bm.backward(g), a.steps, a.warmup)
+        rec = dict(tool="bench_backward", config=cfg, N=N, n=n, m=m, ms=ms, n_active=nact, steps=a.steps, warmup=a.warmup,
+                   forward_ms=round(fwd_ms, 4), forward_setup_kernels_ms=round(setup_ms, 4), forward_solve_kernels_ms=round(solve_ms, 4),
+                   backward_ms=round(bwd_ms, 4), backward_over_forward=round(bwd_ms / fwd_ms, 4),
+                   backward_qps_per_s=round(N / bwd_ms * 1e3), status_ok=ok, optimal=int((r["exitflag"] == 1).sum()),
+                   device=torch.cuda.get_device_name(0), version=daqp_amd.lib().daqp_amd_version().decode())
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+            with open(a.out, "a") as fh:
+                fh.write(line + "\n")
+        bm.close()
+
+
+if __name__ == "__main__":
+    main()
