@@ -68,7 +68,7 @@ EXPORTS = [
     "daqp_batch_device_bytes", "daqp_batch_rechecked", "daqp_batch_set_recheck", "daqp_batch_recheck_ms", "daqp_amd_last_error", "daqp_amd_device_count", "daqp_amd_version", "daqp_amd_has_tiny",
     "setup_daqp_ldp", "daqp_ldp", "ldp2qp_solution", "daqp_extract_result",
     "daqp_minrep_batch", "daqp_minrep_batch_info", "daqp_batch_reset", "reset_daqp_workspace", "daqp_deactivate_constraints",
-    "daqp_batch_backward",
+    "daqp_batch_backward", "daqp_batch_backward_soft",
     "daqp_batch_enable_trace", "daqp_batch_read_trace", "daqp_batch_enable_profile", "daqp_batch_read_profile", "daqp_batch_read_ldp",
 ]
 
@@ -303,6 +303,7 @@ def lib():
     L.daqp_minrep_batch_info.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)]
     L.daqp_batch_reset.argtypes = [vp]
     L.daqp_batch_backward.argtypes = [vp, vp, vp, vp, vp, vp, ci]
+    L.daqp_batch_backward_soft.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
     L.reset_daqp_workspace.argtypes = [vp]
     L.reset_daqp_workspace.restype = None
     L.daqp_deactivate_constraints.argtypes = [vp]

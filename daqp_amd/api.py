@@ -311,14 +311,19 @@ class BatchModel:
         self._out_keep = [o]
         return o
 
+    _BW_KEYS = ("dz", "dbupper", "dblower", "qsoft", "usoft", "usoft_id")
+
     def backward(self, grad_x, out="torch"):
         """The adjoint of the last solve (daqp_batch_backward, include/daqp_amd.h): for grad_x = dl/dx of shape (N, n) returns
         dict(dz, dbupper, dblower, status) with dl/df = -dz, dl/dH = -1/2 (dz x' + x dz'), dl/dA_i = -(lam_i dz + dnu_i x)' on the
         general rows of the working set (dnu = dbupper + dblower), dl/dbupper = dbupper, dl/dblower = dblower.  status (N,) int32:
         0, or why that problem has no derivative (its outputs are zero then).  out='torch': device tensors, grad_x a device tensor,
         nothing waits for the device; out='numpy': host arrays.  Raises unless the last operation on the batch was a successful
-        solve(), and for batches with soft constraints (ns_max > 0)."""
-        N, n, m = self.N, self.n, self.m
+        solve().  A model created with ns_max > 0 goes through daqp_batch_backward_soft: soft rows of the working set enter the
+        system with rho_soft q_k in its (2,2) block, and the dict also holds qsoft (N, m): q_k = c_k H^-1 c_k' on those rows, usoft
+        (N, ns_max, n): u_k = H^-1 c_k' per soft row of the working set, and usoft_id (N, ns_max) int32: their row ids, -1 for unused
+        slots -- what the q_k-dependence terms of dl/dH, dl/dA and dl/drho_soft are made of (daqp_amd.layer.soft_gradient_terms)."""
+        N, n, m, ns = self.N, self.n, self.m, self.ns
         keep = []
         if out == "torch":
             dev = torch.device("cuda", self.device)
@@ -328,7 +333,10 @@ class BatchModel:
             keep.append(g)
             o = dict(dz=torch.empty((N, n), dtype=torch.float64, device=dev), dbupper=torch.empty((N, m), dtype=torch.float64, device=dev),
                      dblower=torch.empty((N, m), dtype=torch.float64, device=dev), status=torch.empty(N, dtype=torch.int32, device=dev))
-            ptrs = [g.data_ptr()] + [o[k].data_ptr() for k in ("dz", "dbupper", "dblower", "status")]
+            if ns > 0:
+                o.update(qsoft=torch.empty((N, m), dtype=torch.float64, device=dev), usoft=torch.empty((N, ns, n), dtype=torch.float64, device=dev),
+                         usoft_id=torch.empty((N, ns), dtype=torch.int32, device=dev))
+            ptrs = [g.data_ptr()] + [o[k].data_ptr() for k in self._BW_KEYS[:3 if ns == 0 else 6]] + [o["status"].data_ptr()]
             mem = MEM_DEVICE
         else:
             g = grad_x.detach().cpu().numpy() if _is_torch(grad_x) else grad_x
@@ -336,11 +344,14 @@ class BatchModel:
             if g.shape != (N, n):
                 raise ValueError(f"grad_x must have shape {(N, n)}")
             o = dict(dz=np.empty((N, n)), dbupper=np.empty((N, m)), dblower=np.empty((N, m)), status=np.empty(N, np.int32))
-            ptrs = [g.ctypes.data] + [o[k].ctypes.data for k in ("dz", "dbupper", "dblower", "status")]
+            if ns > 0:
+                o.update(qsoft=np.empty((N, m)), usoft=np.empty((N, ns, n)), usoft_id=np.empty((N, ns), np.int32))
+            ptrs = [g.ctypes.data] + [o[k].ctypes.data for k in self._BW_KEYS[:3 if ns == 0 else 6]] + [o["status"].ctypes.data]
             mem = MEM_HOST
-        rc = lib().daqp_batch_backward(self._h, *ptrs, mem)
+        entry = "daqp_batch_backward" if ns == 0 else "daqp_batch_backward_soft"
+        rc = getattr(lib(), entry)(self._h, *ptrs, mem)
         if rc != 0:
-            raise RuntimeError(f"daqp_batch_backward failed ({rc}): {_lib.last_error()}")
+            raise RuntimeError(f"{entry} failed ({rc}): {_lib.last_error()}")
         self._bw_keep = [keep, o]      # the launch reads / writes them after this call has returned
         return o
 

@@ -14,12 +14,23 @@
 //     dz  = R^-1 (w - N_W' dnu)
 // The stored LDL' of the solve (L, vecs) and the blocked image Mblk are NOT read: their layout differs per solve kernel family.
 //
+// Soft rows (SOFT == true: batches created with ns_max > 0).  An active row k with DAQP_SOFT in its sense sits at
+// c_k x - b_k = rho_soft q_k lam_k with q_k = c_k H^-1 c_k' = |N_k|^2, so the (2,2) block of the system is -S instead of 0,
+// S = diag(rho_soft q_k on the SOFT rows of W, 0 elsewhere):
+//     (N_W N_W' + S) dnu = N_W w              on the unnormalised Gram matrix G_kk *= 1 + rho_soft; q_k is G_kk itself (not
+//                                             scaling[]: that one has the diag_h and rows < ms special cases), so after the scaling
+//                                             to unit rows the diagonal of a SOFT row is 1 + rho_soft
+// S depends on H and A through q_k, and the caller needs q_k and u_k = H^-1 c_k' = R^-1 N_k' for those terms of dl/dH, dl/dA and
+// dl/drho_soft (include/daqp_amd.h): qsoft[q][id] = q_k, usoft[q][slot] = u_k (unscaled like dz), usoft_id[q][slot] = id, slots in
+// working-set order, ns_max = cap - n - 1 of them per problem, unused ones zero / -1.  DAQP_EXIT_SOFT_OPTIMAL is a differentiable
+// end state then.  SOFT == false compiles to what the kernel was before soft rows: side[] holds 0 / 1 and nothing below is emitted.
+//
 // How R^-1 is stored (daqp_batch_read_ldp shows the same): packed upper, row i at roff(i, n); rows < ms are normalised by
 // scaling[i] (true row = stored row / scaling[i]) unless H was diagonal (QState::diag_h: rows kept as they are).  The division is
 // folded into the vectors that meet those rows (g, the rows of A, the result), so every output is in the caller's unscaled units.
 //
-// Mapping: one workgroup per problem; T = 64 (ONE wavefront, R^-1, the rows and the Gram matrix in LDS) while n <= 64 -- the working
-// set then holds at most 65 rows -- and T = 256 beyond, R^-1 streamed from HBM, rows and Gram matrix in LDS where they fit (NL) and
+// Mapping: one workgroup per problem; T = 64 (ONE wavefront, R^-1, the rows and the Gram matrix in LDS) while n <= 64 and all of it
+// fits (with ns_max = 0 the working set holds at most 65 rows and it always does) -- and T = 256 beyond, R^-1 streamed from HBM, rows and Gram matrix in LDS where they fit (NL) and
 // in a per-WORKGROUP scratch in HBM where they do not (persistent workgroups, problem q, q + grid, ...).  All arithmetic is fp64.
 #pragma once
 #include "batch_dev.hip.h"
@@ -32,6 +43,8 @@ struct BackwardArgs {
     int *status;                  // [N]
     double *scratch;              // [grid][scratch_per_wg] (NL == false), or null
     size_t scratch_per_wg;
+    double *qsoft, *usoft;        // [N][m], [N][ns_max][n]: SOFT kernels only, each may be null
+    int *usoft_id;                // [N][ns_max], may be null
 };
 
 // LDS of one workgroup in bytes: w, g', rs (n each), rhs, y, sn, dg (cap each), then R^-1 (RL), rows + Gram (NL), ids, side, flag
@@ -44,7 +57,7 @@ __host__ __device__ inline size_t backward_lds_bytes(int n, int cap, bool rl, bo
 }
 __host__ __device__ inline size_t backward_scratch_doubles(int n, int cap) { return (size_t)cap * (n | 1) + (size_t)tri(cap); }
 
-template <int T, bool RL, bool NL>
+template <int T, bool RL, bool NL, bool SOFT>
 __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
 {
     extern __shared__ double lds_bw[];
@@ -67,12 +80,18 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
             const int sflag = qs->setup_flag, uflag = qs->upd_flag, eflag = qs->exitflag;
             if (sflag < 0) st = sflag;
             else if (uflag < 0) st = uflag;
-            else if (eflag != DAQP_EXIT_OPTIMAL) st = eflag != 0 ? eflag : DAQP_EXIT_UNSUPPORTED;
+            else if (eflag != DAQP_EXIT_OPTIMAL && !(SOFT && eflag == DAQP_EXIT_SOFT_OPTIMAL)) st = eflag != 0 ? eflag : DAQP_EXIT_UNSUPPORTED;
             else if (qs->n_prox > 0) st = DAQP_EXIT_UNSUPPORTED;
             else if (qs->sing_ind == DAQP_UNCONSTRAINED_OPTIMAL) na = 0;      // the shortcut: W is empty, dz = H^-1 g
             if (st == 0 && (na < 0 || na > cap)) st = DAQP_BACKWARD_SINGULAR;
         }
         for (int r = tid; r < m; r += T) { dbu[r] = 0.0; dbl[r] = 0.0; }
+        const int ns = cap - n - 1;      // ns_max of the batch
+        if constexpr (SOFT) {
+            if (a.qsoft) for (int r = tid; r < m; r += T) a.qsoft[(size_t)q * m + r] = 0.0;
+            if (a.usoft) for (int e = tid; e < ns * n; e += T) a.usoft[(size_t)q * ns * n + e] = 0.0;
+            if (a.usoft_id) for (int s = tid; s < ns; s += T) a.usoft_id[(size_t)q * ns + s] = -1;
+        }
         if (st == 0) {
             const size_t qF = qf(b, q);
             const double *Rg = b.Rinv + qF * b.rtri, *sc = b.scaling + qF * m;
@@ -91,7 +110,12 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
             for (int k = tid; k < na; k += T) {
                 const int id = b.WS[(size_t)q * cap + k];
                 if (id < 0 || id >= m) { ids[k] = 0; side[k] = 0; *bad = 1; }
-                else { ids[k] = id; side[k] = (b.sense[(size_t)q * m + id] & DAQP_LOWER) ? 1 : 0; }
+                else {
+                    const int sg = b.sense[(size_t)q * m + id];
+                    ids[k] = id;
+                    side[k] = (sg & DAQP_LOWER) ? 1 : 0;
+                    if constexpr (SOFT) side[k] |= (sg & DAQP_SOFT) ? 2 : 0;      // bit 1: the row carries rho_soft q_k in S
+                }
             }
             // ---- w = R^-T g
             for (int j = tid; j < n; j += T) {
@@ -134,6 +158,7 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
                 for (int k = tid; k < na; k += T) {
                     const double d = G[tri(k) + k];
                     if (!(d > 0.0)) { sn[k] = 0.0; *bad = 1; } else sn[k] = 1.0 / sqrt(d);
+                    if constexpr (SOFT) { if ((side[k] & 2) && a.qsoft) a.qsoft[(size_t)q * m + ids[k]] = d; }      // q_k = |N_k|^2
                 }
                 __syncthreads();
                 if (*bad) st = DAQP_BACKWARD_SINGULAR;
@@ -141,7 +166,12 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
             if (st == 0 && na > 0) {
                 for (int e = tid; e < na * na; e += T) {
                     const int k = e / na, l = e - k * na;
-                    if (l <= k) G[tri(k) + l] *= sn[k] * sn[l];
+                    if constexpr (SOFT) {
+                        if (l == k && (side[k] & 2)) G[tri(k) + k] *= sn[k] * sn[k] * (1.0 + b.st.rho_soft);      // N_k N_k' + S_kk
+                        else if (l <= k) G[tri(k) + l] *= sn[k] * sn[l];
+                    } else {
+                        if (l <= k) G[tri(k) + l] *= sn[k] * sn[l];
+                    }
                 }
                 for (int k = tid; k < na; k += T) rhs[k] *= sn[k];
                 // ---- Cholesky in place (right-looking), diagonal in dg; a pivot below zero_tol ends it
@@ -185,7 +215,46 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
                     for (int k = 0; k < na; ++k) s -= Nr[(size_t)k * ldn + j] * y[k];
                     gp[j] = s;
                 }
-                for (int k = tid; k < na; k += T) (side[k] ? dbl : dbu)[ids[k]] = y[k];
+                for (int k = tid; k < na; k += T) ((SOFT ? (side[k] & 1) : side[k]) ? dbl : dbu)[ids[k]] = y[k];
+                if constexpr (SOFT) {
+                    if (a.usoft || a.usoft_id) {      // (block-uniform) u_k = R^-1 N_k' of the SOFT rows, in working-set order
+                        int *slot = reinterpret_cast<int *>(dg);      // the Cholesky diagonal is spent: ns < cap ints fit
+                        for (int s = tid; s < ns; s += T) slot[s] = -1;
+                        __syncthreads();
+                        for (int k = tid; k < na; k += T) {
+                            if (!(side[k] & 2)) continue;
+                            int cnt = 0;
+                            for (int l = 0; l < k; ++l) cnt += (side[l] >> 1) & 1;
+                            if (cnt < ns) slot[cnt] = k;
+                        }
+                        __syncthreads();
+                        if (a.usoft_id) for (int s = tid; s < ns; s += T) { if (slot[s] >= 0) a.usoft_id[(size_t)q * ns + s] = ids[slot[s]]; }
+                        if (a.usoft) {
+                            double *uq = a.usoft + (size_t)q * ns * n;
+                            if constexpr (RL) {
+                                for (int e = tid; e < ns * n; e += T) {
+                                    const int s = e / n, i = e - s * n, k = slot[s];
+                                    if (k < 0) continue;
+                                    const double *row = R + roff(i, n), *x1 = Nr + (size_t)k * ldn;
+                                    double acc = 0;
+                                    for (int j = i; j < n; ++j) acc += row[j] * x1[j];
+                                    uq[e] = rs[i] * acc;
+                                }
+                            } else {      // a wave per element, as for dz below
+                                const int lane = tid & 63;
+                                for (int e = tid >> 6; e < ns * n; e += T / 64) {
+                                    const int s = e / n, i = e - s * n, k = slot[s];
+                                    if (k < 0) continue;      // (wave-uniform)
+                                    const double *row = R + roff(i, n), *x1 = Nr + (size_t)k * ldn;
+                                    double acc = 0;
+                                    for (int j = i + lane; j < n; j += 64) acc += row[j] * x1[j];
+                                    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+                                    if (lane == 0) uq[e] = rs[i] * acc;
+                                }
+                            }
+                        }
+                    }
+                }
             } else if (st == 0) {
                 for (int j = tid; j < n; j += T) gp[j] = w[j];
             }
@@ -212,6 +281,7 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
             }
         }
         if (st != 0) for (int i = tid; i < n; i += T) dzq[i] = 0.0;
+        if constexpr (SOFT) { if (st != 0 && a.qsoft) for (int r = tid; r < m; r += T) a.qsoft[(size_t)q * m + r] = 0.0; }
         if (tid == 0) a.status[q] = st;
         __syncthreads();      // the next problem of this workgroup reuses everything
     }

@@ -3,7 +3,11 @@
 #include "backward.hip.h"
 
 namespace daqp_amd {
-template __global__ void k_backward<64, true, true>(BatchDev, BackwardArgs);
-template __global__ void k_backward<256, false, true>(BatchDev, BackwardArgs);
-template __global__ void k_backward<256, false, false>(BatchDev, BackwardArgs);
+template __global__ void k_backward<64, true, true, false>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, true, false>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, false, false>(BatchDev, BackwardArgs);
+// batches created with ns_max > 0: soft rows in the (2,2) block, q_k and u_k emitted
+template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
 }

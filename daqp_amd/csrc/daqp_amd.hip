@@ -76,9 +76,12 @@ extern template __global__ void k_ldp_wg<2, true>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, false>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, true>(BatchDev, int);
 // the adjoint kernel: backward_kernel.hip
-extern template __global__ void k_backward<64, true, true>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<256, false, true>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<256, false, false>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<64, true, true, false>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, true, false>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, false, false>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
 }
 
 using namespace daqp_amd;
@@ -238,6 +241,8 @@ struct DAQPBatch {
     int bw_grid = 0;
     double *bw_g = nullptr, *bw_dz = nullptr, *bw_dbu = nullptr, *bw_dbl = nullptr;   // staging of host-resident arguments
     int *bw_status = nullptr;
+    double *bw_qsoft = nullptr, *bw_usoft = nullptr;   // the same for daqp_batch_backward_soft's extra outputs (each allocated when first asked for)
+    int *bw_uid = nullptr;
 };
 
 namespace {
@@ -1977,24 +1982,31 @@ int daqp_batch_working_sets(DAQPBatch *b, int *n_active_host, int *ws_host)
 
 // The adjoint of the last solve (include/daqp_amd.h, backward.hip.h): one launch on the batch's stream.  Refusals come before any
 // device work.  Host-resident arguments go through the batch's own staging buffers and the call waits for the results; device-resident
-// ones are used in place and nothing waits.
-int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory)
+// ones are used in place and nothing waits.  Batches created with ns_max > 0 run the SOFT instantiations (soft rows in the (2,2)
+// block, q_k / u_k emitted where asked for); every other batch runs the kernels it ran before there were any.
+static int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
+                           c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory)
 {
-    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported"); return DAQP_EXIT_UNSUPPORTED; }
     if (!b->is_setup || !b->solved || b->pending_mask) {
-        set_err("daqp_batch_backward: the last operation on the batch was not a successful daqp_batch_solve");
+        set_err("%s: the last operation on the batch was not a successful daqp_batch_solve", who);
         return DAQP_EXIT_UNSUPPORTED;
     }
     HIPCHK(hipSetDevice(b->device));
     const BatchDev &d = b->d;
-    const size_t N = d.N, n = d.n, m = d.m;
-    // ---- which instantiation: one wavefront with everything in LDS (n <= 64), a workgroup with rows + Gram matrix in LDS, or in scratch
-    const bool small = d.n <= 64;
+    const size_t N = d.N, n = d.n, m = d.m, ns = b->ns_max;
+    const bool soft = b->ns_max > 0;
+    if (!soft) qsoft = nullptr, usoft = nullptr, usoft_id = nullptr;      // (ns_max == 0: usoft / usoft_id are empty, qsoft is zeroed below)
+    // ---- which instantiation: one wavefront with everything in LDS (n <= 64, and cap = n + ns_max + 1 rows and their Gram matrix
+    // fit), a workgroup with rows + Gram matrix in LDS, or in scratch
+    const size_t lds_max = (size_t)144 * 1024;
+    const bool small = d.n <= 64 && backward_lds_bytes(d.n, d.cap, true, true) <= lds_max;
     const size_t lds_nl = backward_lds_bytes(d.n, d.cap, small, true);
-    const bool nl = small || lds_nl <= (size_t)144 * 1024;
+    const bool nl = small || lds_nl <= lds_max;
     const size_t lds = nl ? lds_nl : backward_lds_bytes(d.n, d.cap, false, false);
-    void (*kb)(BatchDev, BackwardArgs) = small ? k_backward<64, true, true> : (nl ? k_backward<256, false, true> : k_backward<256, false, false>);
+    if (lds > lds_max) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
+    void (*kb)(BatchDev, BackwardArgs);
+    if (soft) kb = small ? k_backward<64, true, true, true> : (nl ? k_backward<256, false, true, true> : k_backward<256, false, false, true>);
+    else kb = small ? k_backward<64, true, true, false> : (nl ? k_backward<256, false, true, false> : k_backward<256, false, false, false>);
     BackwardArgs a{};
     int grid = d.N;
     if (!nl) {
@@ -2011,13 +2023,19 @@ int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_floa
         a.scratch = b->bw_scratch;
         grid = b->bw_grid;
     }
-    if (memory == DAQP_MEM_DEVICE) { a.grad_x = grad_x; a.dz = dz; a.dbupper = dbupper; a.dblower = dblower; a.status = status; }
-    else {
+    if (memory == DAQP_MEM_DEVICE) {
+        a.grad_x = grad_x; a.dz = dz; a.dbupper = dbupper; a.dblower = dblower; a.status = status;
+        a.qsoft = qsoft; a.usoft = usoft; a.usoft_id = usoft_id;
+    } else {
         if (!b->bw_status && (dev_alloc(b, &b->bw_g, N * n) || dev_alloc(b, &b->bw_dz, N * n) || dev_alloc(b, &b->bw_dbu, N * m) ||
                          dev_alloc(b, &b->bw_dbl, N * m) || dev_alloc(b, &b->bw_status, N)))
             return DAQP_EXIT_UNSUPPORTED;
+        if (qsoft && !b->bw_qsoft && dev_alloc(b, &b->bw_qsoft, N * m)) return DAQP_EXIT_UNSUPPORTED;
+        if (usoft && !b->bw_usoft && dev_alloc(b, &b->bw_usoft, N * ns * n)) return DAQP_EXIT_UNSUPPORTED;
+        if (usoft_id && !b->bw_uid && dev_alloc(b, &b->bw_uid, N * ns)) return DAQP_EXIT_UNSUPPORTED;
         HIPCHK(hipMemcpyAsync(b->bw_g, grad_x, N * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
         a.grad_x = b->bw_g; a.dz = b->bw_dz; a.dbupper = b->bw_dbu; a.dblower = b->bw_dbl; a.status = b->bw_status;
+        a.qsoft = qsoft ? b->bw_qsoft : nullptr; a.usoft = usoft ? b->bw_usoft : nullptr; a.usoft_id = usoft_id ? b->bw_uid : nullptr;
     }
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kb, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
@@ -2026,10 +2044,35 @@ int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_floa
         HIPCHK(hipMemcpyAsync(dz, b->bw_dz, N * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
         if (m) HIPCHK(hipMemcpyAsync(dbupper, b->bw_dbu, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
         if (m) HIPCHK(hipMemcpyAsync(dblower, b->bw_dbl, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (qsoft && m) HIPCHK(hipMemcpyAsync(qsoft, b->bw_qsoft, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (usoft) HIPCHK(hipMemcpyAsync(usoft, b->bw_usoft, N * ns * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (usoft_id) HIPCHK(hipMemcpyAsync(usoft_id, b->bw_uid, N * ns * sizeof(int), hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipMemcpyAsync(status, b->bw_status, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
     }
     return 0;
+}
+
+int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory)
+{
+    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported: daqp_batch_backward_soft"); return DAQP_EXIT_UNSUPPORTED; }
+    return backward_launch("daqp_batch_backward", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory);
+}
+
+// The same for batches with soft rows (and, with identical results, for batches without): q_k, u_k and the ids of the SOFT rows of
+// each working set come back with the adjoint.  A batch with ns_max == 0 has none: its qsoft is zero, usoft / usoft_id are empty.
+int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
+                             c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory)
+{
+    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_soft: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
+    const int rc = backward_launch("daqp_batch_backward_soft", b, grad_x, dz, dbupper, dblower, qsoft, usoft, usoft_id, status, memory);
+    if (rc == 0 && b->ns_max == 0 && qsoft && b->d.m) {      // no SOFT instantiation ran: no row of any working set is soft
+        const size_t bytes = sizeof(double) * (size_t)b->d.N * b->d.m;
+        if (memory == DAQP_MEM_DEVICE) HIPCHK(hipMemsetAsync(qsoft, 0, bytes, b->stream));
+        else memset(qsoft, 0, bytes);
+    }
+    return rc;
 }
 
 int daqp_batch_kernel_ms(DAQPBatch *b, float *setup_ms, float *solve_ms)

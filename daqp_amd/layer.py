@@ -1,24 +1,59 @@
 """A batch of QPs as a differentiable torch operation (OptNet-style QP layer, learned condensed MPC).
 
-    x = qp_layer(H, f, A, bupper, blower)          # (N, n), differentiable in H, f, A, bupper, blower
+    x = qp_layer(H, f, A, bupper, blower)                                  # (N, n), differentiable in H, f, A, bupper, blower
+    x = qp_layer(H, f, A, bupper, blower, sense=sense, rho_soft=rho)       # rows with DAQP_SOFT in sense may be violated at a price
 
-Forward is a BatchModel setup + solve on the inputs' device and current stream.  Backward is ONE daqp_batch_backward call -- the
-adjoint system at the stored working set, on the factor the solve kept (include/daqp_amd.h) -- followed by a few torch
-operations that form only the gradients somebody asked for:
+Forward is a BatchModel setup + solve on the inputs' device and current stream.  Backward is ONE daqp_batch_backward call
+(daqp_batch_backward_soft when sense has SOFT rows) -- the adjoint system at the stored working set, on the factor the solve kept
+(include/daqp_amd.h) -- followed by a few torch operations that form only the gradients somebody asked for:
 
     dl/df = -dz      dl/dH = -1/2 (dz x' + x dz')      dl/dA_i = -(lam_i dz + dnu_i x)'      dl/dbupper, dl/dblower = dbupper, dblower
 
-Out of scope: soft constraints, problems that went through the proximal loop (singular H, LPs), gradients of lam or fval.
+An active SOFT row k sits at c_k x - b_k = rho_soft q_k lam_k, q_k = c_k H^-1 c_k': the system's (2,2) block is -S, S = diag(rho_soft
+q_k), and since q_k depends on H and A their gradients gain a term each (soft_gradient_terms below; dsig_k = dnu_k lam_k, u_k = H^-1 c_k'):
+
+    dl/drho_soft = sum_k dsig_k q_k      dl/dH -= rho_soft sum_k dsig_k u_k u_k'      dl/dA_i += 2 rho_soft dsig_i u_i'
+
+Out of scope: problems that went through the proximal loop (singular H, LPs), gradients of lam, fval or soft_slack, per-row soft weights.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
 from .api import INF, UPDATE_unconstrained, BatchModel
 
+SOFT = 8      # DAQP_SOFT (include/daqp_amd.h)
+
+
+def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms):
+    """The terms that S = diag(rho_soft q_k), q_k = c_k H^-1 c_k', adds to the gradients of a batch with active SOFT rows, from what
+    BatchModel.backward returns for it: lam (N, m) of the solve, dnu = dbupper + dblower (N, m), qsoft (N, m), usoft (N, ns, n),
+    usoft_id (N, ns) (-1: unused slot).  Pure torch, any device.  Returns per problem
+
+        dH   (N, n, n)       -rho_soft sum_k dsig_k u_k u_k'              add to -1/2 (dz x' + x dz')
+        dA   (N, m - ms, n)  +2 rho_soft dsig_i u_i' on the SOFT general rows of W, zero elsewhere (a soft simple bound has c_k = e_k,
+                             no row of A)                                  add to -(lam_i dz + dnu_i x)'
+        drho (N,)            sum_k dsig_k q_k
+
+    with dsig_k = dnu_k lam_k on the SOFT rows of W."""
+    N, ns, n = usoft.shape
+    m = lam.shape[1]
+    valid = usoft_id >= 0
+    idx = usoft_id.clamp(min=0).long()
+    dsig = torch.gather(dnu * lam, 1, idx) * valid                                   # (N, ns), working-set order
+    su = (rho_soft * dsig)[:, :, None] * usoft                                        # rho dsig_k u_k
+    dH = -torch.einsum("qsi,qsj->qij", su, usoft)
+    general = (valid & (idx >= ms))[:, :, None]
+    row = (idx - ms).clamp(min=0)[:, :, None].expand(N, ns, n)
+    dA = torch.zeros((N, m - ms, n), dtype=usoft.dtype, device=usoft.device)
+    if m > ms:
+        dA.scatter_add_(1, row, 2.0 * su * general)
+    drho = (dnu * lam * qsoft).sum(1)                                                 # qsoft is zero off the SOFT rows of W
+    return dict(dH=dH, dA=dA, drho=drho)
+
 
 class _QPLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings):
+    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft):
         if not f.is_cuda:
             raise ValueError("qp_layer needs its inputs on the GPU")
         N, n = f.shape
@@ -32,14 +67,28 @@ class _QPLayer(torch.autograd.Function):
             raise ValueError(f"m = {m} bounds for ms = {ms} simple bounds and {mA} rows of A")
         c = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
         bl = torch.full_like(bupper, -INF).detach() if blower is None else blower
+        ns_max = 0
+        if sense is not None:
+            sense = torch.as_tensor(sense).detach().to(device=f.device, dtype=torch.int32)
+            if sense.dim() == 1:
+                sense = sense.expand(N, m)
+            if tuple(sense.shape) != (N, m):
+                raise ValueError(f"sense must have shape {(N, m)} or {(m,)}")
+            sense = sense.contiguous()
+            ns_max = int(((sense & SOFT) != 0).sum(1).max())
+        settings = dict(settings)
+        if rho_soft is not None:
+            settings["rho_soft"] = float(rho_soft)
         with torch.cuda.device(f.device):      # the model takes that device's current stream
-            bm = BatchModel(N, n, m, ms, 0, device=f.device.index, **settings)
+            bm = BatchModel(N, n, m, ms, ns_max, device=f.device.index, **settings)
             if shared:
-                bm.setup_shared(c(H), c(f), c(A), c(bupper), c(bl))
+                bm.setup_shared(c(H), c(f), c(A), c(bupper), c(bl), sense)
             else:
-                bm.setup(c(H), c(f), c(A), c(bupper), c(bl), init_mask=UPDATE_unconstrained)
+                bm.setup(c(H), c(f), c(A), c(bupper), c(bl), sense, init_mask=UPDATE_unconstrained)
             r = bm.solve(out="torch")
         ctx.bm, ctx.x, ctx.lam = bm, r["x"], r["lam"]
+        ctx.rho = bm._settings.rho_soft
+        ctx.rho_like = rho_soft if isinstance(rho_soft, torch.Tensor) else None
         ctx.ms, ctx.shared, ctx.strict, ctx.info = ms, shared, strict, info
         if info is not None:
             info["exitflag"] = r["exitflag"]
@@ -63,9 +112,14 @@ class _QPLayer(torch.autograd.Function):
                                    f"{int(status[q])}); strict=False gives them zero gradients")
         dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
         need = ctx.needs_input_grad
-        gH = gf = gA = gbu = gbl = None
+        gH = gf = gA = gbu = gbl = grho = None
+        soft = None
+        if "usoft" in o and (need[0] or need[2] or need[10]):      # the q_k-dependence of S
+            soft = soft_gradient_terms(lam, dbu + dbl, o["qsoft"], o["usoft"], o["usoft_id"], ctx.rho, ms)
         if need[0]:
             gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
+            if soft is not None:
+                gH = gH + soft["dH"]
             if ctx.shared:
                 gH = gH.sum(0)
         if need[1]:
@@ -76,21 +130,32 @@ class _QPLayer(torch.autograd.Function):
                 gA = -(lg.t() @ dz + ng.t() @ x)
             else:
                 gA = -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
+            if soft is not None:
+                gA = gA + (soft["dA"].sum(0) if ctx.shared else soft["dA"])
         if need[3]:
             gbu = dbu
         if need[4]:
             gbl = dbl
-        return gH, gf, gA, gbu, gbl, None, None, None, None
+        if need[10]:
+            like = ctx.rho_like
+            grho = soft["drho"].sum() if soft is not None else torch.zeros((), dtype=torch.float64, device=x.device)
+            grho = grho.to(device=like.device, dtype=like.dtype).reshape(like.shape)
+        return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho
 
 
-def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, **settings):
+def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, **settings):
     """x* (N, n) of  min 1/2 x'Hx + f'x  s.t.  blower <= [x[:ms]; A x] <= bupper  for N problems, differentiable.
 
     H (N, n, n), f (N, n), A (N, mA, n) or None, bupper / blower (N, m) with m = ms + mA (ms defaults to m - mA; blower None =
     no lower bounds).  H of shape (n, n) together with A of shape (mA, n) is ONE plant for the whole batch (BatchModel.setup_shared);
     their gradients are then the sums over the batch.  **settings are DAQP settings (primal_tol=..., iter_limit=...).
 
+    sense (N, m) or (m,) int32, not differentiable: the reference's sense bits per row; rows with DAQP_SOFT (8) may be violated, an
+    active one sits rho_soft q_k lam_k beyond its bound (q_k = c_k H^-1 c_k').  The batch is created with ns_max = the largest number
+    of SOFT rows of a problem.  rho_soft: a float or a 0-dim tensor (default: the DAQP setting, 1e-6); a tensor that requires grad
+    receives dl/drho_soft summed over the batch.  info["exitflag"] holds 2 (DAQP_EXIT_SOFT_OPTIMAL) where a soft row is violated.
+
     Backward raises if a problem has no derivative (it was not solved to optimality, it went through the proximal loop, or its
     active constraints are linearly dependent).  strict=False gives such problems zero gradients instead; pass info={} to read
     info["exitflag"] (after forward) and info["status"] (after backward), both (N,) int32 device tensors."""
-    return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings))
+    return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft)

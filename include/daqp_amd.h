@@ -46,7 +46,7 @@ typedef double c_float; /* the path computes in fp64 only (reference types.h:8-1
 #define DAQP_EXIT_OVERDETERMINED_INITIAL -6
 #define DAQP_EXIT_TIMELIMIT -7
 #define DAQP_EXIT_UNSUPPORTED -8
-/* per-problem status of daqp_batch_backward only (never an exit flag of a solve): the Gram matrix of the active rows is numerically
+/* per-problem status of daqp_batch_backward / daqp_batch_backward_soft only (never an exit flag of a solve): the Gram matrix of the active rows is numerically
    singular (a pivot of its Cholesky factor below settings->zero_tol) -- linearly dependent active constraints, no unique adjoint */
 #define DAQP_BACKWARD_SINGULAR -20
 
@@ -313,10 +313,38 @@ int daqp_batch_reset(DAQPBatch *b);
  * Returns nonzero, with the reason in the last-error string and without any device work, when
  *   - the last operation on the batch was not a successful daqp_batch_solve (a setup, update or reset since then invalidates
  *     the stored optimum),
- *   - the batch was created with ns_max > 0: SOFT CONSTRAINTS ARE OUT OF SCOPE (they change the (2,2) block of the system),
+ *   - the batch was created with ns_max > 0: SOFT CONSTRAINTS ARE OUT OF SCOPE of this entry point (they change the (2,2) block
+ *     of the system and need more outputs): daqp_batch_backward_soft below takes such batches,
  *   - a pointer is NULL.
  * Not differentiated: lam, fval. */
 int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory);
+/* The same adjoint for batches with soft rows (created with ns_max > 0; DAQP_SOFT in a row's sense).  An active soft row k is not
+ * held at its bound b_k but at  c_k x - b_k = rho_soft q_k lam_k  with  q_k = c_k H^-1 c_k'  (the solver adds settings->rho_soft to
+ * the diagonal of the NORMALISED M_W M_W'; lam is in the caller's units).  The optimum therefore solves
+ *
+ *        [ H    C_W' ] [ x   ]   [ -f  ]
+ *        [ C_W  -S   ] [ lam ] = [ b_W ],      S = diag(rho_soft q_k for the SOFT rows of W, 0 for the others)
+ *
+ * and the adjoint for g = dl/dx is the same symmetric matrix:  H dz + C_W' dnu = g,  C_W dz - S dnu = 0.  dz, dbupper, dblower and
+ * status are as above, with DAQP_EXIT_SOFT_OPTIMAL a differentiable end state like DAQP_EXIT_OPTIMAL.  S depends on H and A through
+ * q_k, which adds a term to their gradients; with  dsig_k = dnu_k lam_k  on the SOFT rows of W and  u_k = H^-1 c_k':
+ *
+ *        dl/df        = -dz                         dl/dbupper, dl/dblower = dbupper, dblower
+ *        dl/drho_soft = sum_k dsig_k q_k
+ *        dl/dH        = -1/2 (dz x' + x dz')  -  rho_soft sum_k dsig_k u_k u_k'
+ *        dl/dA_i      = -(lam_i dz + dnu_i x)'  +  2 rho_soft dsig_i u_i'      general rows i in W; the second term for SOFT ones only
+ *
+ * (a soft simple bound, k < ms, has c_k = e_k: its u_k term goes to dl/dH only).  Leaving the u_k terms out keeps dl/df and the
+ * bound gradients right and makes dl/dH and dl/dA wrong.  What they need comes back in three more arrays, each of which may be NULL:
+ *   qsoft     N*m          q_k for the SOFT rows of W, zero for every other row
+ *   usoft     N*ns_max*n   u_k, one n-vector per SOFT row of W, in working-set order; unused slots are zero
+ *   usoft_id  N*ns_max     the row ids k of those vectors; unused slots are -1
+ * Preconditions, stream and memory semantics are those of daqp_batch_backward (`memory` applies to all eight arrays); ns_max > 0
+ * is not a refusal here, and for ns_max == 0 dz, dbupper, dblower and status are bit for bit those of daqp_batch_backward (qsoft is
+ * zero, usoft and usoft_id are empty).  Not differentiated: lam, fval, soft_slack.  Per-row soft weights do not exist here. */
+int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
+                             c_float *qsoft /* N*m */, c_float *usoft /* N*ns_max*n */, int *usoft_id /* N*ns_max */,
+                             int *status, int memory);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Time of BatchModel.backward next to the forward step it follows, at the two headline shapes of BASELINE.md.
 
-  python tools/bench_backward.py [--configs C2,C3] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
+  python tools/bench_backward.py [--configs C2,C3] [--soft] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
 
 Per shape: N device-resident QPs (daqp_amd.synthetic.generate_batch_torch), forward = BatchModel.setup + solve with device outputs,
 backward = one BatchModel.backward on a device-resident grad_x; both timed with HIP events around K calls after W warm-up calls
-(device time, the stream drained before and after).  One JSON line per shape is printed and appended to --out."""
+(device time, the stream drained before and after).  One JSON line per shape is printed and appended to --out.
+--soft: the same shapes with NS_SOFT rows per problem made SOFT and violated at the generator's optimum (rho_soft = RHO_SOFT), the batch
+created with ns_max = NS_SOFT: the SOFT instantiations of the adjoint kernel, with qsoft / usoft / usoft_id written."""
 import argparse
 import json
 import os
@@ -13,6 +15,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+NS_SOFT, RHO_SOFT = 2, 0.3
 SHAPES = {"C2": (50, 150, 0, 20, 20_000), "C3": (12, 48, 0, 5, 100_000)}     # n, m, ms, n_active, default batch
 
 
@@ -33,6 +36,7 @@ def timed(fn, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C2,C3")
+    ap.add_argument("--soft", action="store_true")
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -45,10 +49,21 @@ def main():
         n, m, ms, nact, N = SHAPES[cfg]
         N = a.batch or N
         q = generate_batch_torch(N, n, m, ms, nact, seed=1)
-        bm = daqp_amd.BatchModel(N, n, m, ms)
+        sense = None
+        if a.soft:      # the NS_SOFT general rows furthest from their bounds at the optimum: soft, upper bound 0.2 .. 0.5 below their value there
+            ax = torch.einsum("qik,qk->qi", q["A"], q["xref"])
+            slack = torch.minimum(q["bupper"][:, ms:] - ax, ax - q["blower"][:, ms:])
+            rows = slack.topk(NS_SOFT, dim=1).indices
+            sense = torch.zeros((N, m), dtype=torch.int32, device="cuda")
+            sense.scatter_(1, rows + ms, 8)
+            gen = torch.Generator(device="cuda").manual_seed(2)
+            bu = ax.gather(1, rows) - (0.2 + 0.3 * torch.rand((N, NS_SOFT), dtype=torch.float64, device="cuda", generator=gen))
+            q["bupper"].scatter_(1, rows + ms, bu)
+            q["blower"].scatter_(1, rows + ms, bu - 1.0)
+        bm = daqp_amd.BatchModel(N, n, m, ms, NS_SOFT, rho_soft=RHO_SOFT) if a.soft else daqp_amd.BatchModel(N, n, m, ms)
 
         def forward():
-            bm.setup(q["H"], q["f"], q["A"], q["bupper"], q["blower"])
+            bm.setup(q["H"], q["f"], q["A"], q["bupper"], q["blower"], sense)
             return bm.solve(out="torch")
 
         r = forward()
@@ -62,6 +77,8 @@ def main():
                    forward_ms=round(fwd_ms, 4), forward_setup_kernels_ms=round(setup_ms, 4), forward_solve_kernels_ms=round(solve_ms, 4),
                    backward_ms=round(bwd_ms, 4), backward_over_forward=round(bwd_ms / fwd_ms, 4),
                    backward_qps_per_s=round(N / bwd_ms * 1e3), status_ok=ok, optimal=int((r["exitflag"] == 1).sum()),
+                   **(dict(soft=True, ns_max=NS_SOFT, rho_soft=RHO_SOFT, soft_optimal=int((r["exitflag"] == 2).sum()),
+                           soft_rows_active=int((o["usoft_id"] >= 0).sum())) if a.soft else {}),
                    device=torch.cuda.get_device_name(0), version=daqp_amd.lib().daqp_amd_version().decode())
         line = json.dumps(rec)
         print(line, flush=True)
