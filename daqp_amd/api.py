@@ -48,7 +48,8 @@ def _ip(a):
 # single problem: same call shape as the reference binding
 # ---------------------------------------------------------------------------
 def solve(H, f, A, bupper, blower=None, sense=None, **settings):
-    """x, fval, exitflag, info = solve(H, f, A, bupper, blower, sense, primal_tol=..., iter_limit=...)"""
+    """x, fval, exitflag, info = solve(H, f, A, bupper, blower, sense, primal_tol=..., iter_limit=...)
+    info carries the reference binding's keys and, beyond them, 'soft_slack' (DAQPResult.soft_slack, which daqp.pyx does not pass on)."""
     H, f, A, bupper = _np64(H), _np64(f), _np64(A), _np64(bupper)
     n, m = f.size, bupper.size
     mA = A.shape[0] if (A is not None and A.ndim == 2) else 0
@@ -65,7 +66,8 @@ def solve(H, f, A, bupper, blower=None, sense=None, **settings):
     else:
         info_err = ""
     return x, res.fval, res.exitflag, {"solve_time": res.solve_time, "setup_time": res.setup_time,
-                                       "iterations": res.iter, "nodes": res.nodes, "lam": lam, "error": info_err}
+                                       "iterations": res.iter, "nodes": res.nodes, "lam": lam, "soft_slack": res.soft_slack,
+                                       "error": info_err}
 
 
 class Model:
@@ -140,13 +142,14 @@ class Model:
         return lib().daqp_update_ldp(int(mask), self._ws, C.byref(self._problem()))
 
     def solve(self):
+        """x, fval, exitflag, info as solve(); info['soft_slack'] is an extension over the reference binding"""
         if self._ws is None:
             raise RuntimeError("Model.solve called before setup")
         x, lam = np.empty(self.n), np.empty(self.m)
         res = DAQPResult(_dp(x), _dp(lam), 0, 0, 0, 0, 0, 0, 0)
         lib().daqp_solve(C.byref(res), self._ws)
         return x, res.fval, res.exitflag, {"solve_time": res.solve_time, "setup_time": 0.0, "iterations": res.iter,
-                                           "nodes": res.nodes, "lam": lam}
+                                           "nodes": res.nodes, "lam": lam, "soft_slack": res.soft_slack}
 
     def reset(self):
         """daqp_deactivate_constraints + reset_daqp_workspace: the next solve starts from an empty working set on the LDP as it is."""

@@ -165,11 +165,12 @@ class OracleModel:
         a = self._hold(H=_f64(H), f=_f64(f), A=_f64(A), bu=_f64(bupper), bl=_f64(blower), sense=_i32(sense))
         return self.o.lib.ora_update(self.h, mask, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), _dp(a[4]), _ip(a[5]))
 
-    def solve(self):
+    def solve(self, with_soft=False):
+        """(x, lam, fval, exitflag, iterations); with_soft=True appends the soft slack (DAQPResult.soft_slack, api.c:484)"""
         x, lam = np.zeros(self.n), np.zeros(self.m)
         fval, it, ss = C.c_double(0), C.c_int(0), C.c_double(0)
         flag = self.o.lib.ora_solve(self.h, _dp(x), _dp(lam), C.byref(fval), C.byref(it), C.byref(ss))
-        return x, lam, fval.value, flag, it.value
+        return (x, lam, fval.value, flag, it.value, ss.value) if with_soft else (x, lam, fval.value, flag, it.value)
 
     def state(self):
         na = C.c_int(0)
@@ -304,11 +305,12 @@ class ReferenceModel:
                 self.keep[k] = v
         return self.r.lib.daqp_update_ldp(mask, self.ws, C.byref(self._qp()))
 
-    def solve(self):
+    def solve(self, with_soft=False):
         x, lam = np.zeros(self.n), np.zeros(self.m)
         res = _Result(_dp(x), _dp(lam), 0, 0, 0, 0, 0, 0, 0)
         self.r.lib.daqp_solve(C.byref(res), self.ws)
-        return x, lam, res.fval, res.exitflag, res.iter
+        out = (x, lam, res.fval, res.exitflag, res.iter)
+        return out + (res.soft_slack,) if with_soft else out
 
     def set_primal_start(self, x):
         x = _f64(x)

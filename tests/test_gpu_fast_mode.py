@@ -50,6 +50,7 @@ def test_fast_mode_shapes(oracle, gpu_lib, shape):
     assert np.array_equal(g["exitflag"], ref[3]) and np.array_equal(g["iter"], ref[4])
     assert np.array_equal(np.sign(g["lam"]), np.sign(ref[1]))
     assert np.abs(g["x"] - ref[0]).max() < XTOL
+    assert np.abs(g["lam"] - ref[1]).max() < 1e-8 and np.abs(g["fval"] - ref[2]).max() < 1e-8 * max(1.0, np.abs(ref[2]).max())
 
 
 @pytest.mark.parametrize("shape,rows", [((64, 128, 0, 20), 0), ((64, 100, 0, 63), 0), ((64, 128, 8, 64), 0), ((56, 120, 4, 20), 5), ((56, 120, 4, 20), 14),
@@ -182,6 +183,7 @@ def test_fast_mode_workgroup_kernel_shapes(oracle, gpu_lib, shape):
     assert np.array_equal(g["exitflag"], ref[3]) and np.array_equal(g["iter"], ref[4])
     assert np.array_equal(np.sign(g["lam"]), np.sign(ref[1]))
     assert np.abs(g["x"] - ref[0]).max() < XTOL
+    assert np.abs(g["lam"] - ref[1]).max() < 1e-8 and np.abs(g["fval"] - ref[2]).max() < 1e-8 * max(1.0, np.abs(ref[2]).max())
 
 
 def test_fast_mode_ldp_close(oracle, gpu_lib):
