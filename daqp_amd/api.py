@@ -316,7 +316,7 @@ class BatchModel:
 
     _BW_KEYS = ("dz", "dbupper", "dblower", "qsoft", "usoft", "usoft_id")
 
-    def backward(self, grad_x, out="torch"):
+    def backward(self, grad_x, out="torch", nullspace=False):
         """The adjoint of the last solve (daqp_batch_backward, include/daqp_amd.h): for grad_x = dl/dx of shape (N, n) returns
         dict(dz, dbupper, dblower, status) with dl/df = -dz, dl/dH = -1/2 (dz x' + x dz'), dl/dA_i = -(lam_i dz + dnu_i x)' on the
         general rows of the working set (dnu = dbupper + dblower), dl/dbupper = dbupper, dl/dblower = dblower.  status (N,) int32:
@@ -325,8 +325,15 @@ class BatchModel:
         solve().  A model created with ns_max > 0 goes through daqp_batch_backward_soft: soft rows of the working set enter the
         system with rho_soft q_k in its (2,2) block, and the dict also holds qsoft (N, m): q_k = c_k H^-1 c_k' on those rows, usoft
         (N, ns_max, n): u_k = H^-1 c_k' per soft row of the working set, and usoft_id (N, ns_max) int32: their row ids, -1 for unused
-        slots -- what the q_k-dependence terms of dl/dH, dl/dA and dl/drho_soft are made of (daqp_amd.layer.soft_gradient_terms)."""
+        slots -- what the q_k-dependence terms of dl/dH, dl/dA and dl/drho_soft are made of (daqp_amd.layer.soft_gradient_terms).
+
+        nullspace=True: daqp_batch_backward_nullspace with which = 0 -- problems that went through the proximal loop (singular H,
+        LPs; status -8 otherwise) get their adjoint from the null-space kernel on the caller's own H, every other problem comes
+        out bit for bit as without it.  nullspace="all": which = 1, every problem through that kernel.  n <= 64 ("all" is refused
+        beyond, True leaves the -8), ns_max == 0, and H / A given as device tensors must still be alive and unchanged."""
         N, n, m, ns = self.N, self.n, self.m, self.ns
+        if nullspace not in (False, True, "all"):
+            raise ValueError('nullspace must be False, True or "all"')
         keep = []
         if out == "torch":
             dev = torch.device("cuda", self.device)
@@ -339,7 +346,7 @@ class BatchModel:
             if ns > 0:
                 o.update(qsoft=torch.empty((N, m), dtype=torch.float64, device=dev), usoft=torch.empty((N, ns, n), dtype=torch.float64, device=dev),
                          usoft_id=torch.empty((N, ns), dtype=torch.int32, device=dev))
-            ptrs = [g.data_ptr()] + [o[k].data_ptr() for k in self._BW_KEYS[:3 if ns == 0 else 6]] + [o["status"].data_ptr()]
+            ptrs = [g.data_ptr()] + [o[k].data_ptr() for k in self._BW_KEYS[:3 if (ns == 0 or nullspace) else 6]] + [o["status"].data_ptr()]
             mem = MEM_DEVICE
         else:
             g = grad_x.detach().cpu().numpy() if _is_torch(grad_x) else grad_x
@@ -349,10 +356,14 @@ class BatchModel:
             o = dict(dz=np.empty((N, n)), dbupper=np.empty((N, m)), dblower=np.empty((N, m)), status=np.empty(N, np.int32))
             if ns > 0:
                 o.update(qsoft=np.empty((N, m)), usoft=np.empty((N, ns, n)), usoft_id=np.empty((N, ns), np.int32))
-            ptrs = [g.ctypes.data] + [o[k].ctypes.data for k in self._BW_KEYS[:3 if ns == 0 else 6]] + [o["status"].ctypes.data]
+            ptrs = [g.ctypes.data] + [o[k].ctypes.data for k in self._BW_KEYS[:3 if (ns == 0 or nullspace) else 6]] + [o["status"].ctypes.data]
             mem = MEM_HOST
-        entry = "daqp_batch_backward" if ns == 0 else "daqp_batch_backward_soft"
-        rc = getattr(lib(), entry)(self._h, *ptrs, mem)
+        if nullspace:
+            entry = "daqp_batch_backward_nullspace"      # (refuses ns_max > 0 itself)
+            rc = lib().daqp_batch_backward_nullspace(self._h, *ptrs, 1 if nullspace == "all" else 0, mem)
+        else:
+            entry = "daqp_batch_backward" if ns == 0 else "daqp_batch_backward_soft"
+            rc = getattr(lib(), entry)(self._h, *ptrs, mem)
         if rc != 0:
             raise RuntimeError(f"{entry} failed ({rc}): {_lib.last_error()}")
         self._bw_keep = [keep, o]      # the launch reads / writes them after this call has returned

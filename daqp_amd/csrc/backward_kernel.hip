@@ -1,6 +1,7 @@
-// backward_kernel.hip -- translation unit of the adjoint kernel (backward.hip.h)
+// backward_kernel.hip -- translation unit of the adjoint kernels (backward.hip.h, nullspace.hip.h)
 #include <hip/hip_runtime.h>
 #include "backward.hip.h"
+#include "nullspace.hip.h"
 
 namespace daqp_amd {
 template __global__ void k_backward<64, true, true, false>(BatchDev, BackwardArgs);
@@ -10,4 +11,6 @@ template __global__ void k_backward<256, false, false, false>(BatchDev, Backward
 template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
 template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
 template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
+// the null-space adjoint: the caller's H instead of the kept factor (singular H, LPs)
+template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
 }

@@ -28,6 +28,7 @@
 #include "setup_blk.hip.h"
 #include "minrep.hip.h"
 #include "backward.hip.h"
+#include "nullspace.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -82,6 +83,7 @@ extern template __global__ void k_backward<256, false, false, false>(BatchDev, B
 extern template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
 }
 
 using namespace daqp_amd;
@@ -1984,8 +1986,11 @@ int daqp_batch_working_sets(DAQPBatch *b, int *n_active_host, int *ws_host)
 // device work.  Host-resident arguments go through the batch's own staging buffers and the call waits for the results; device-resident
 // ones are used in place and nothing waits.  Batches created with ns_max > 0 run the SOFT instantiations (soft rows in the (2,2)
 // block, q_k / u_k emitted where asked for); every other batch runs the kernels it ran before there were any.
+// nsw: the null-space kernel (nullspace.hip.h) on the same stream -- -1: not at all; 0: behind k_backward, for the problems that went
+// through the proximal loop only (it overwrites their outputs; every other problem keeps k_backward's bits); 1: instead of k_backward,
+// for every problem.  Launched for n <= 64 only: beyond, nsw == 0 leaves k_backward's DAQP_EXIT_UNSUPPORTED and nsw == 1 was refused.
 static int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
-                           c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory)
+                           c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory, int nsw = -1)
 {
     if (!b->is_setup || !b->solved || b->pending_mask) {
         set_err("%s: the last operation on the batch was not a successful daqp_batch_solve", who);
@@ -2003,13 +2008,13 @@ static int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x,
     const size_t lds_nl = backward_lds_bytes(d.n, d.cap, small, true);
     const bool nl = small || lds_nl <= lds_max;
     const size_t lds = nl ? lds_nl : backward_lds_bytes(d.n, d.cap, false, false);
-    if (lds > lds_max) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
+    if (lds > lds_max && nsw != 1) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
     void (*kb)(BatchDev, BackwardArgs);
     if (soft) kb = small ? k_backward<64, true, true, true> : (nl ? k_backward<256, false, true, true> : k_backward<256, false, false, true>);
     else kb = small ? k_backward<64, true, true, false> : (nl ? k_backward<256, false, true, false> : k_backward<256, false, false, false>);
     BackwardArgs a{};
     int grid = d.N;
-    if (!nl) {
+    if (!nl && nsw != 1) {
         a.scratch_per_wg = backward_scratch_doubles(d.n, d.cap);
         if (!b->bw_scratch) {
             // persistent workgroups, at most 512 of them and at most 256 MiB of scratch
@@ -2037,9 +2042,21 @@ static int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x,
         a.grad_x = b->bw_g; a.dz = b->bw_dz; a.dbupper = b->bw_dbu; a.dblower = b->bw_dbl; a.status = b->bw_status;
         a.qsoft = qsoft ? b->bw_qsoft : nullptr; a.usoft = usoft ? b->bw_usoft : nullptr; a.usoft_id = usoft_id ? b->bw_uid : nullptr;
     }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kb, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
-    HIPCHK(hipGetLastError());
+    if (nsw != 1) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kb, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (nsw >= 0 && d.n <= 64) {
+        NullspaceArgs na{};
+        na.grad_x = a.grad_x; na.dz = a.dz; na.dbupper = a.dbupper; na.dblower = a.dblower; na.status = a.status;
+        na.lp = (b->ident && d.H == b->ident) ? 1 : 0;
+        na.only_prox = nsw == 0 ? 1 : 0;
+        const size_t lds_ns = nullspace_lds_bytes(d.n);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_backward_nullspace<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ns));
+        hipLaunchKernelGGL(k_backward_nullspace<64>, dim3(d.N), dim3(64), lds_ns, b->stream, d, na);
+        HIPCHK(hipGetLastError());
+    }
     if (memory != DAQP_MEM_DEVICE) {
         HIPCHK(hipMemcpyAsync(dz, b->bw_dz, N * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
         if (m) HIPCHK(hipMemcpyAsync(dbupper, b->bw_dbu, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
@@ -2058,6 +2075,18 @@ int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_floa
     if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
     if (b->ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported: daqp_batch_backward_soft"); return DAQP_EXIT_UNSUPPORTED; }
     return backward_launch("daqp_batch_backward", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory);
+}
+
+// The adjoint without a factor of H (nullspace.hip.h): which == 0 -- daqp_batch_backward, then the null-space kernel for the problems
+// that went through the proximal loop; which == 1 -- the null-space kernel for every problem.  It reads the caller's H and A in place.
+int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int which, int memory)
+{
+    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_nullspace: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->ns_max > 0) { set_err("daqp_batch_backward_nullspace: batches created with ns_max > 0 (soft constraints) are not supported: q_k = c_k H^-1 c_k' does not exist for a singular H"); return DAQP_EXIT_UNSUPPORTED; }
+    if (which != 0 && which != 1) { set_err("daqp_batch_backward_nullspace: which must be 0 (proximal problems only) or 1 (every problem)"); return DAQP_EXIT_UNSUPPORTED; }
+    if (which == 1 && b->d.n > 64) { set_err("daqp_batch_backward_nullspace: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", b->d.n); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->is_setup && b->d.H == nullptr) { set_err("daqp_batch_backward_nullspace: the batch has no Hessian of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
+    return backward_launch("daqp_batch_backward_nullspace", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory, which);
 }
 
 // The same for batches with soft rows (and, with identical results, for batches without): q_k, u_k and the ids of the SOFT rows of

@@ -14,7 +14,14 @@ q_k), and since q_k depends on H and A their gradients gain a term each (soft_gr
 
     dl/drho_soft = sum_k dsig_k q_k      dl/dH -= rho_soft sum_k dsig_k u_k u_k'      dl/dA_i += 2 rho_soft dsig_i u_i'
 
-Out of scope: problems that went through the proximal loop (singular H, LPs), gradients of lam, fval or soft_slack, per-row soft weights.
+Problems that went through the proximal loop (a positive semi-definite H, or H=None: an LP batch) have no factor of H to solve
+that system on; qp_layer(..., nullspace=True) sends them through daqp_batch_backward_nullspace instead -- the null-space method on
+the caller's own H: QR of the active rows, Cholesky of Z'HZ -- and the same formulas give the gradients (an LP has no dl/dH).  Such
+a problem is differentiable where its optimum is locally unique: independent active rows (R_jj^2 >= zero_tol) and Z'HZ positive
+definite (pivots > zero_tol max(1, max_i H_ii)); an LP must sit at a vertex.  n <= 64, no SOFT rows.
+
+Out of scope: gradients of lam, fval or soft_slack, per-row soft weights, proximal problems with n > 64 or with SOFT rows, an LP
+with one shared A.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -53,13 +60,18 @@ def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms):
 
 class _QPLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft):
+    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft, nullspace=False):
         if not f.is_cuda:
             raise ValueError("qp_layer needs its inputs on the GPU")
         N, n = f.shape
         m = bupper.shape[1]
-        shared = H.dim() == 2
-        if A is not None and (A.dim() == 2) != shared:
+        if H is None and nullspace:      # an LP batch
+            if A is not None and A.dim() == 2:
+                raise ValueError("H=None (an LP batch) goes with A of shape (N, mA, n): a shared-plant LP is not supported")
+            shared = False
+        else:
+            shared = H.dim() == 2
+        if A is not None and H is not None and (A.dim() == 2) != shared:
             raise ValueError("H of shape (n, n) goes with A of shape (mA, n): one plant for the whole batch")
         mA = 0 if A is None else A.shape[-2]
         ms = m - mA if ms is None else int(ms)
@@ -90,6 +102,7 @@ class _QPLayer(torch.autograd.Function):
         ctx.rho = bm._settings.rho_soft
         ctx.rho_like = rho_soft if isinstance(rho_soft, torch.Tensor) else None
         ctx.ms, ctx.shared, ctx.strict, ctx.info = ms, shared, strict, info
+        ctx.nullspace = bool(nullspace)
         if info is not None:
             info["exitflag"] = r["exitflag"]
             info["lam"] = r["lam"]
@@ -100,7 +113,7 @@ class _QPLayer(torch.autograd.Function):
     def backward(ctx, grad_x):
         bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
         with torch.cuda.device(x.device):
-            o = bm.backward(grad_x.to(torch.float64).contiguous(), out="torch")
+            o = bm.backward(grad_x.to(torch.float64).contiguous(), out="torch", nullspace=ctx.nullspace)
         status = o["status"]
         if ctx.info is not None:
             ctx.info["status"] = status
@@ -140,10 +153,10 @@ class _QPLayer(torch.autograd.Function):
             like = ctx.rho_like
             grho = soft["drho"].sum() if soft is not None else torch.zeros((), dtype=torch.float64, device=x.device)
             grho = grho.to(device=like.device, dtype=like.dtype).reshape(like.shape)
-        return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho
+        return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho, None
 
 
-def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, **settings):
+def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, nullspace=False, **settings):
     """x* (N, n) of  min 1/2 x'Hx + f'x  s.t.  blower <= [x[:ms]; A x] <= bupper  for N problems, differentiable.
 
     H (N, n, n), f (N, n), A (N, mA, n) or None, bupper / blower (N, m) with m = ms + mA (ms defaults to m - mA; blower None =
@@ -157,5 +170,12 @@ def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sens
 
     Backward raises if a problem has no derivative (it was not solved to optimality, it went through the proximal loop, or its
     active constraints are linearly dependent).  strict=False gives such problems zero gradients instead; pass info={} to read
-    info["exitflag"] (after forward) and info["status"] (after backward), both (N,) int32 device tensors."""
-    return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft)
+    info["exitflag"] (after forward) and info["status"] (after backward), both (N,) int32 device tensors.
+
+    nullspace=True: backward is daqp_batch_backward_nullspace -- problems that went through the proximal loop are differentiated
+    too (null-space method on H itself; n <= 64, no SOFT rows), every other problem as without it.  H may then be a positive
+    semi-definite matrix, or None: an LP batch with per-problem A (N, mA, n) -- dl/dH is None, dl/df, dl/dA, dl/dbupper and
+    dl/dblower come from the same formulas with the x and lam of the solve.  An LP is differentiable at a vertex only."""
+    if nullspace and sense is not None and bool(((torch.as_tensor(sense) & SOFT) != 0).any()):
+        raise ValueError("qp_layer: nullspace=True does not take SOFT rows")
+    return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, nullspace)

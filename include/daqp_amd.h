@@ -22,7 +22,8 @@
  *
  * Only the hot path is implemented: dense convex H (a singular one, and an LP
  * with H == NULL, go through the reference's proximal outer loop, daqp_prox.c);
- * sense bits ACTIVE/LOWER/IMMUTABLE/SOFT.  Binary constraints, hierarchies and AVIs
+ * sense bits ACTIVE/LOWER/IMMUTABLE/SOFT.  Solutions are differentiable (daqp_batch_backward, daqp_batch_backward_soft; problems
+ * that went through the proximal loop, n <= 64: daqp_batch_backward_nullspace).  Binary constraints, hierarchies and AVIs
  * (the reference's bnb/hiqp/avi loops) return DAQP_EXIT_UNSUPPORTED.  There is NO CPU fallback: without a HIP device every
  * entry point fails with DAQP_EXIT_UNSUPPORTED and daqp_amd_last_error() says why.
  */
@@ -47,7 +48,9 @@ typedef double c_float; /* the path computes in fp64 only (reference types.h:8-1
 #define DAQP_EXIT_TIMELIMIT -7
 #define DAQP_EXIT_UNSUPPORTED -8
 /* per-problem status of daqp_batch_backward / daqp_batch_backward_soft only (never an exit flag of a solve): the Gram matrix of the active rows is numerically
-   singular (a pivot of its Cholesky factor below settings->zero_tol) -- linearly dependent active constraints, no unique adjoint */
+   singular (a pivot of its Cholesky factor below settings->zero_tol) -- linearly dependent active constraints, no unique adjoint.
+   daqp_batch_backward_nullspace reports it for the same reason (R_jj^2 < zero_tol in the QR of the unit active rows) and when H is
+   not positive definite on the null space of the active rows (a pivot of Z'HZ <= zero_tol max(1, max_i H_ii)) */
 #define DAQP_BACKWARD_SINGULAR -20
 
 /* ---- daqp_update_ldp masks (reference include/constants.h:54-61) ---- */
@@ -303,7 +306,8 @@ int daqp_batch_reset(DAQPBatch *b);
  *                  (every dnu_i goes to exactly one of the two; an equality row, bupper == blower, may appear on either side;
  *                   dnu = dbupper + dblower)
  *   status   N     0: done.  The problem's exit flag when its solve (or setup / update) did not end DAQP_EXIT_OPTIMAL;
- *                  DAQP_EXIT_UNSUPPORTED when it went through the proximal loop (singular H, LP); DAQP_BACKWARD_SINGULAR when
+ *                  DAQP_EXIT_UNSUPPORTED when it went through the proximal loop (singular H, LP: daqp_batch_backward_nullspace
+ *                  below differentiates those); DAQP_BACKWARD_SINGULAR when
  *                  the active rows are linearly dependent.  All three outputs of such a problem are zero.
  * x and lam are those of the solve, in the caller's units like everything here.  A problem that took the unconstrained shortcut
  * has W empty: dz = H^-1 g.  A batch set up with shared H and A is supported; the outputs are per problem (dl/dH and dl/dA of
@@ -345,6 +349,39 @@ int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_floa
 int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
                              c_float *qsoft /* N*m */, c_float *usoft /* N*ns_max*n */, int *usoft_id /* N*ns_max */,
                              int *status, int memory);
+/* The same adjoint WITHOUT a factor of H: the null-space method on the caller's own Hessian, for the problems that went through the
+ * proximal loop (singular H; an LP batch, H == NULL).  Their kept factor is that of H + eps I, so daqp_batch_backward answers
+ * DAQP_EXIT_UNSUPPORTED for them; the system
+ *
+ *        [ H    C_W' ] [ dz  ]   [ g ]
+ *        [ C_W  0    ] [ dnu ] = [ 0 ]
+ *
+ * is nonsingular all the same whenever the optimum is locally unique: C_W of full row rank and Z'HZ positive definite, Z a basis of
+ * the null space of C_W.  Per problem (one wavefront, fp64): the k = n_active rows of C_W scaled to unit length; Householder QR
+ * C_W' = Q [R; 0] without pivoting; Hr = Z'HZ with Z the last n - k columns of Q, Cholesky; then
+ *
+ *        dz = Z Hr^-1 Z' g          dnu = R^-1 Q1' (g - H dz), row scaling undone
+ *
+ * Singularity tests, both DAQP_BACKWARD_SINGULAR: R_jj^2 < settings->zero_tol (dependent active rows: what daqp_batch_backward's
+ * Gram Cholesky tests on the same unit rows; more than n rows are dependent), and a pivot of Hr <= zero_tol max(1, max_i H_ii) (H
+ * is not positive definite on the null space: no unique adjoint).  An LP has H = 0: its optimum must be a vertex (k == n, dz = 0),
+ * anything else is singular.  The system contains neither x nor lam: the outputs depend on H, A and W only, not on how tightly the
+ * proximal loop converged.  dz, dbupper, dblower and status mean what they mean for daqp_batch_backward (the formulas for dl/df,
+ * dl/dH, dl/dA, dl/dbupper, dl/dblower are the same, with the x and lam of the solve; an LP has no dl/dH); a nonzero status --
+ * the setup / update / exit flag of a problem that did not end DAQP_EXIT_OPTIMAL, or DAQP_BACKWARD_SINGULAR -- zeroes all three.
+ *   which == 0   daqp_batch_backward runs first; the null-space kernel then runs on the same stream for the problems with
+ *                n_prox > 0 only and overwrites their outputs.  Every other problem comes out bit for bit as daqp_batch_backward
+ *                gives it.
+ *   which == 1   every problem goes through the null-space kernel: a second, independent algorithm for positive definite H.
+ * Preconditions, stream, memory semantics and refusals are those of daqp_batch_backward (`memory` applies to all five arrays).
+ * The kernel reads H and A where the last setup / update left them: device-resident inputs were adopted, not copied, so -- as for
+ * the second pass of INFEASIBLE verdicts (daqp_batch_set_recheck) -- THEY MUST STILL BE VALID AT THIS CALL.  H is taken symmetric.
+ * Left as it is:
+ *   - n > 64: the kernel holds a problem in one wavefront.  With which == 0 proximal problems of such a batch keep
+ *     DAQP_EXIT_UNSUPPORTED; which == 1 is refused for it.
+ *   - batches created with ns_max > 0 are refused: q_k = c_k H^-1 c_k' of a soft row does not exist for a singular H. */
+int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status,
+                                  int which, int memory);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 

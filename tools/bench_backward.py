@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Time of BatchModel.backward next to the forward step it follows, at the two headline shapes of BASELINE.md.
 
-  python tools/bench_backward.py [--configs C2,C3] [--soft] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
+  python tools/bench_backward.py [--configs C2,C3] [--soft | --nullspace] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
 
 Per shape: N device-resident QPs (daqp_amd.synthetic.generate_batch_torch), forward = BatchModel.setup + solve with device outputs,
 backward = one BatchModel.backward on a device-resident grad_x; both timed with HIP events around K calls after W warm-up calls
 (device time, the stream drained before and after).  One JSON line per shape is printed and appended to --out.
 --soft: the same shapes with NS_SOFT rows per problem made SOFT and violated at the generator's optimum (rho_soft = RHO_SOFT), the batch
-created with ns_max = NS_SOFT: the SOFT instantiations of the adjoint kernel, with qsoft / usoft / usoft_id written."""
+created with ns_max = NS_SOFT: the SOFT instantiations of the adjoint kernel, with qsoft / usoft / usoft_id written.
+--nullspace: on the same positive definite batch, BatchModel.backward(nullspace="all") -- every problem through the null-space
+kernel (daqp_batch_backward_nullspace, which = 1) -- timed next to the Gram adjoint and the forward step; the largest difference
+between the two adjoints, relative to the max norm of the Gram adjoint's [dz; dnu], goes into the record."""
 import argparse
 import json
 import os
@@ -37,11 +40,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C2,C3")
     ap.add_argument("--soft", action="store_true")
+    ap.add_argument("--nullspace", action="store_true")
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "backward_bench.jsonl"))
     a = ap.parse_args()
+    if a.soft and a.nullspace:
+        ap.error("--nullspace does not take soft rows")
     import torch
     import daqp_amd
     from daqp_amd.synthetic import generate_batch_torch
@@ -73,12 +79,22 @@ def main():
         fwd_ms = timed(forward, a.steps, a.warmup)
         setup_ms, solve_ms = bm.kernel_ms()
         bwd_ms = timed(lambda: bm.backward(g), a.steps, a.warmup)
+        extra = {}
+        if a.nullspace:
+            o2 = bm.backward(g, nullspace="all")
+            scale = torch.maximum(o["dz"].abs().amax(1), (o["dbupper"] + o["dblower"]).abs().amax(1))
+            diff = torch.maximum((o2["dz"] - o["dz"]).abs().amax(1), (o2["dbupper"] + o2["dblower"] - o["dbupper"] - o["dblower"]).abs().amax(1))
+            both = (o["status"] == 0) & (o2["status"] == 0)
+            ns_ms = timed(lambda: bm.backward(g, nullspace="all"), a.steps, a.warmup)
+            extra = dict(nullspace=True, nullspace_ms=round(ns_ms, 4), nullspace_over_backward=round(ns_ms / bwd_ms, 4),
+                         nullspace_over_forward=round(ns_ms / fwd_ms, 4), nullspace_qps_per_s=round(N / ns_ms * 1e3),
+                         nullspace_status_ok=int((o2["status"] == 0).sum()), nullspace_max_rel_diff=float((diff / scale)[both].max()))
         rec = dict(tool="bench_backward", config=cfg, N=N, n=n, m=m, ms=ms, n_active=nact, steps=a.steps, warmup=a.warmup,
                    forward_ms=round(fwd_ms, 4), forward_setup_kernels_ms=round(setup_ms, 4), forward_solve_kernels_ms=round(solve_ms, 4),
                    backward_ms=round(bwd_ms, 4), backward_over_forward=round(bwd_ms / fwd_ms, 4),
                    backward_qps_per_s=round(N / bwd_ms * 1e3), status_ok=ok, optimal=int((r["exitflag"] == 1).sum()),
                    **(dict(soft=True, ns_max=NS_SOFT, rho_soft=RHO_SOFT, soft_optimal=int((r["exitflag"] == 2).sum()),
-                           soft_rows_active=int((o["usoft_id"] >= 0).sum())) if a.soft else {}),
+                           soft_rows_active=int((o["usoft_id"] >= 0).sum())) if a.soft else {}), **extra,
                    device=torch.cuda.get_device_name(0), version=daqp_amd.lib().daqp_amd_version().decode())
         line = json.dumps(rec)
         print(line, flush=True)
