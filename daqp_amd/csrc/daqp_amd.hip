@@ -2656,11 +2656,12 @@ int daqp_minrep_batch(int *is_redundant, const c_float *A, const c_float *rhs, i
     if (rc) return rc;
     BatchDev &d = b->d;
     int *dev_out = nullptr, *other = nullptr;
+    double *rowscale = nullptr;      // 1 / |A_i| per row of every polyhedron (d.scaling itself is 1: minrep.hip.h)
     const double *dA = nullptr, *db = nullptr;
     auto run = [&]() -> int {
         HIPCHK(hipSetDevice(b->device));
         if (stage(b, A, memory, (size_t)P * d.mA * n, &b->sA, &b->nA, &dA) || stage(b, rhs, memory, (size_t)N, &b->sbu, &b->nbu, &db)) return DAQP_EXIT_UNSUPPORTED;
-        if (dev_alloc(b, &b->structural, (size_t)N) || dev_alloc(b, &other, 1)) return DAQP_EXIT_UNSUPPORTED;
+        if (dev_alloc(b, &b->structural, (size_t)N) || dev_alloc(b, &rowscale, (size_t)N) || dev_alloc(b, &other, 1)) return DAQP_EXIT_UNSUPPORTED;
         if (memory == DAQP_MEM_DEVICE) dev_out = is_redundant;
         else if (dev_alloc(b, &dev_out, (size_t)N)) return DAQP_EXIT_UNSUPPORTED;
         HIPCHK(hipMemsetAsync(other, 0, sizeof(int), b->stream));
@@ -2670,9 +2671,9 @@ int daqp_minrep_batch(int *is_redundant, const c_float *A, const c_float *rhs, i
         b->pending_mask = 0; b->part_mask = 0; b->n_prox_qps = 0; b->reg_pending = false; b->exact_sticky = false;
         b->fresh = false;          // no second pass (recheck.hip.h re-runs a QP setup from H / A, which do not exist here)
         HIPCHK(hipEventRecord(b->ev[0], b->stream));
-        hipLaunchKernelGGL(k_minrep_setup, dim3(P), dim3(256), 0, b->stream, d, dA, b->structural);
+        hipLaunchKernelGGL(k_minrep_setup, dim3(P), dim3(256), 0, b->stream, d, dA, b->structural, rowscale);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_minrep_init, dim3(N), dim3(64), 0, b->stream, d, db, (const int *)b->structural);
+        hipLaunchKernelGGL(k_minrep_init, dim3(N), dim3(64), 0, b->stream, d, db, (const int *)b->structural, (const double *)rowscale);
         HIPCHK(hipGetLastError());
         b->is_setup = true;
         int r2 = launch_ldp(b, 1);      // the pinned row enters the working set (utils.c:817-818)

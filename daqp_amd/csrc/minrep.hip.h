@@ -8,9 +8,14 @@
 // after them:
 //   k_minrep_setup   a workgroup per polyhedron: rows of A normalised to unit length (as the QP setup does: the fp32 screen of the
 //                    image kernels certifies its margin for rows of norm <= 1 only), the blocked fp64 image, its fp32 copy where
-//                    the workgroup kernel wants one, scaling, the structural bits of vanishing rows, and the identity-factor state
-//                    of the LP path (R^-1 = I, RinvD = 1)
-//   k_minrep_init    a wave per test: d = b * scaling, dlower = -1e30, v = 0, the sense with the pinned row, a fresh record
+//                    the workgroup kernel wants one, the rows' factors 1 / |A_i| (rowscale), the structural bits of vanishing rows,
+//                    and the identity-factor state of the LP path (R^-1 = I, RinvD = 1).  BatchDev::scaling is 1 for every row: the
+//                    solve kernels compare a slack with primal_tol * scaling (auxiliary.c:110,136: the QP path's way of holding
+//                    the RAW slack to primal_tol), and here the normalised rows ARE the problem -- primal_tol is held against the
+//                    slack in units of the row's length, whatever scale the caller's rows have (with scaling = 1 / |A_i| a row of
+//                    length 1e-2 was let through with a normalised slack of -1e-4, and a redundant row that clears its bound by
+//                    less was kept)
+//   k_minrep_init    a wave per test: d = b * rowscale, dlower = -1e30, v = 0, the sense with the pinned row, a fresh record
 //   k_minrep_verdict exit flags -> is_redundant (INFEASIBLE: 1, a vanishing row: -1, anything else: 0), other flags than OPTIMAL /
 //                    INFEASIBLE counted
 //   k_reset          daqp_deactivate_constraints and / or reset_daqp_workspace for every problem of a batch
@@ -21,13 +26,13 @@ namespace daqp_amd {
 
 constexpr int kResetDeactivate = 1, kResetWorkspace = 2;
 
-__global__ __launch_bounds__(256) void k_minrep_setup(BatchDev b, const double *A, int *structural)
+__global__ __launch_bounds__(256) void k_minrep_setup(BatchDev b, const double *A, int *structural, double *rowscale)
 {
     const int p = blockIdx.x, tid = threadIdx.x;
     const int n = b.n, m = b.m, ms = b.ms, mA = b.mA;
     double2 *Mq = reinterpret_cast<double2 *>(b.Mblk + (size_t)p * b.nblk * b.npair * 128);
     float *M32 = b.M32 ? b.M32 + (size_t)p * b.nblk * b.nquad * 256 : nullptr;
-    double *sc = b.scaling + (size_t)p * m;
+    double *sc = b.scaling + (size_t)p * m, *rs = rowscale + (size_t)p * m;
     int *str = structural + (size_t)p * m;
     const double *Ap = A + (size_t)p * mA * n;
     // R^-1 = I, packed upper triangle (the back-transformation of the solve kernels reads it)
@@ -57,16 +62,17 @@ __global__ __launch_bounds__(256) void k_minrep_setup(BatchDev b, const double *
             if (d32) { float *q4 = d32 + (size_t)(t >> 1) * 256 + 2 * (t & 1); q4[0] = (float)w.x; q4[1] = (float)w.y; }
         }
         if (d32 && (b.npair & 1)) { float *q4 = d32 + (size_t)(b.npair >> 1) * 256 + 2; q4[0] = 0.0f; q4[1] = 0.0f; }
-        sc[r] = scal;
+        sc[r] = 1.0;
+        rs[r] = scal;
         str[r] = sbits;
     }
 }
 
-__global__ __launch_bounds__(64) void k_minrep_init(BatchDev b, const double *rhs, const int *structural)
+__global__ __launch_bounds__(64) void k_minrep_init(BatchDev b, const double *rhs, const int *structural, const double *rowscale)
 {
     const int q = blockIdx.x, lane = threadIdx.x, m = b.m, n = b.n;
     const int p = q / m, i = q - p * m;
-    const double *sc = b.scaling + (size_t)p * m, *bp = rhs + (size_t)p * m;
+    const double *sc = rowscale + (size_t)p * m, *bp = rhs + (size_t)p * m;
     const int *str = structural + (size_t)p * m;
     const int pinned = !(str[i] & DAQP_IMMUTABLE);
     for (int r = lane; r < m; r += 64) {
