@@ -91,7 +91,19 @@ typedef struct {
 typedef struct {
     c_float primal_tol, dual_tol, zero_tol, pivot_tol, progress_tol;
     int cycle_tol, iter_limit;
-    c_float fval_bound;
+    c_float fval_bound;         /* the dual-objective stop (daqp.c:10,20): at every dual-feasible iterate the least-distance problem's
+                                   1/2 (|u|^2 + soft slack) -- the fval this library reports plus 1/2 f'H^-1 f -- is compared with fval_bound,
+                                   and the first iterate where it is strictly greater ends the solve with DAQP_EXIT_INFEASIBLE (-1): the
+                                   optimal value cannot be below that (weak duality).  At this exit, as in the reference (api.c:27 skips
+                                   ldp2qp_solution): fval is the dual value of that iterate, a lower bound of the optimum; lam holds its
+                                   multipliers in the least-distance problem's units (row k of the QP: lam_k / sqrt(c_k H^-1 c_k')), zero
+                                   off the working set; soft_slack belongs to the same iterate; x is the iterate in the least-distance
+                                   problem's coordinates, not a point of the QP, and iter counts up to the stop.  A later daqp_solve /
+                                   daqp_batch_solve with a larger bound continues from the kept working set.  On a cold default-mode
+                                   batch solve the problems stopped this way report -1 and so take the second pass in the exact
+                                   arithmetic with the others of that verdict (daqp_batch_rechecked counts them; see below), under
+                                   the same bound: their outputs are the exact mode's.  Inside the proximal loop (singular H, LPs) the
+                                   bound applies to each inner least-distance problem.  DAQP_INF: off. */
     c_float eps_prox, eta_prox; /* shift / stationarity tolerance of the proximal loop (singular H); < 0: automatic */
     c_float rho_soft;
     c_float rel_subopt, abs_subopt;

@@ -93,6 +93,8 @@ typedef struct {
     const int *qsense;
     /* optional event trace: +(id+1) add, -(id+1) remove */
     int *trace; int trace_cap, trace_len;
+    /* optional level trace: w->fval at every dual-feasible iterate, i.e. every value the fval_bound test of ldp_loop sees */
+    double *levels; int levels_cap, levels_len;
 } ora_work;
 
 static int tri(int k) { return k * (k + 1) / 2; }                 /* DAQP_ARSUM */
@@ -163,6 +165,13 @@ void ora_free(ora_work *w)
 
 void ora_set_trace(ora_work *w, int *buf, int cap) { w->trace = buf; w->trace_cap = cap; w->trace_len = 0; }
 int ora_trace_len(const ora_work *w) { return w->trace_len; }
+/* the levels the fval_bound test compares with 2 * fval_bound (daqp.c:20): w->fval = |u|^2 + soft slack at every dual-feasible iterate
+ * since the buffer was set, inner solves of the proximal loop included */
+void ora_set_levels(ora_work *w, double *buf, int cap) { w->levels = buf; w->levels_cap = cap; w->levels_len = 0; }
+int ora_levels_len(const ora_work *w) { return w->levels_len; }
+double ora_get_fval(const ora_work *w) { return w->fval; }          /* the internal objective the last solve ended with */
+void ora_set_settings(ora_work *w, const ora_settings *st) { w->st = *st; }   /* work->settings changed between two daqp_solve calls */
+void ora_get_settings(const ora_work *w, ora_settings *st) { *st = w->st; }
 
 static void reset_ws(ora_work *w) /* daqp.c:142-146 */
 {
@@ -543,6 +552,8 @@ static int ldp_loop(ora_work *w)
             solve_csp(w);
             if (remove_blocking(w)) continue;
             primal_and_fval(w);
+            if (w->levels && w->levels_len < w->levels_cap) w->levels[w->levels_len] = w->fval;
+            w->levels_len++;
             if (w->fval > fbound) { flag = ORA_EXIT_INFEASIBLE; break; }
             if (!add_infeasible(w)) {
                 double dmin = w->D[0];

@@ -98,6 +98,15 @@ class Oracle:
         L.ora_get_prox.argtypes = [C.c_void_p, c_int_p, c_int_p]
         L.ora_set_primal_start.argtypes = [C.c_void_p, c_double_p]
         L.ora_set_primal_start.restype = None
+        L.ora_set_levels.argtypes = [C.c_void_p, c_double_p, C.c_int]
+        L.ora_set_levels.restype = None
+        L.ora_levels_len.argtypes = [C.c_void_p]
+        L.ora_get_fval.argtypes = [C.c_void_p]
+        L.ora_get_fval.restype = C.c_double
+        L.ora_set_settings.argtypes = [C.c_void_p, C.POINTER(Settings)]
+        L.ora_set_settings.restype = None
+        L.ora_get_settings.argtypes = [C.c_void_p, C.POINTER(Settings)]
+        L.ora_get_settings.restype = None
 
     def quadprog(self, H, f, A, bupper, blower, sense=None, settings=None):
         H, f, A, bupper, blower, sense = _f64(H), _f64(f), _f64(A), _f64(bupper), _f64(blower), _i32(sense)
@@ -149,6 +158,35 @@ class OracleModel:
         direction, refine, refactor repair, cycle-guard rebuild -- the GPU kernels' traces carry the same codes)"""
         t = self.trace[: self.o.lib.ora_trace_len(self.h)].copy()
         return t if marks else t[t < TRACE_MARK]
+
+    def enable_levels(self, cap=20000):
+        """record w->fval (|u|^2 + soft slack) at every dual-feasible iterate from now on: the values daqp_ldp compares with
+        2 * fval_bound (daqp.c:20), one per pass through that test, inner solves of the proximal loop included"""
+        self._levels = np.zeros(cap)
+        self.o.lib.ora_set_levels(self.h, _dp(self._levels), cap)
+
+    def get_levels(self, restart=True):
+        """the levels recorded since enable_levels / the last call with restart=True"""
+        k = self.o.lib.ora_levels_len(self.h)
+        assert k <= self._levels.size, "level trace overflow"
+        out = self._levels[:k].copy()
+        if restart:
+            self.o.lib.ora_set_levels(self.h, _dp(self._levels), self._levels.size)
+        return out
+
+    def internal_fval(self):
+        """w->fval as the last solve left it"""
+        return self.o.lib.ora_get_fval(self.h)
+
+    def settings(self, **kw):
+        """change the workspace's settings between solves (work->settings->... = ...); returns the Settings in force"""
+        st = Settings()
+        self.o.lib.ora_get_settings(self.h, C.byref(st))
+        for k, v in kw.items():
+            setattr(st, k, v)
+        if kw:
+            self.o.lib.ora_set_settings(self.h, C.byref(st))
+        return st
 
     def _hold(self, **kw):
         for k, v in kw.items():

@@ -93,6 +93,97 @@ def edge_cases(rng):
     return cases
 
 
+def levels_of(ora, q, settings=None):
+    """the levels |u|^2 + soft slack of every dual-feasible iterate of daqp_quadprog(q) on the oracle (inner solves of the proximal
+    loop included), and the solve's (x, lam, fval, flag, iter)"""
+    n, m = q["f"].size, q["bupper"].size
+    A = np.ascontiguousarray(q["A"], dtype=np.float64).reshape(-1, n)
+    sense = q.get("sense")
+    om = ora.model(n, m, m - A.shape[0], ns=0 if sense is None else int((np.asarray(sense) & O.SOFT != 0).sum()), settings=settings)
+    om.enable_levels()
+    if om.setup(q["H"], q["f"], A, q["bupper"], q["blower"], sense, init_mask=O.UPDATE_unconstrained | O.UPDATE_eliminate) < 0:
+        return np.zeros(0), None
+    r = om.solve()
+    return om.get_levels(), r
+
+
+def bounds_from_levels(lv, rng):
+    """fval_bound values for one problem out of its levels: [(tag, bound)] -- below the first level; between two neighbouring levels
+    picked by rng; exactly half a level (the test is >, so that iterate goes on) and the double just below (it stops there); above
+    the last level (nothing stops)"""
+    u = np.unique(lv)
+    out = [("first", 0.5 * u[0] - 1.0), ("none", 0.5 * u[-1] + 1.0)]
+    if u.size > 1:
+        j = int(rng.integers(1, u.size))
+        out.append((f"mid{j}", 0.25 * (u[j - 1] + u[j])))
+        out.append((f"at{j}", 0.5 * u[j]))
+        out.append((f"below{j}", float(np.nextafter(0.5 * u[j], -np.inf))))
+    return out
+
+
+def fval_bound_cases(ora, small=False):
+    """(name, q, settings kw) of the fval_bound cases (daqp.c:10,20): the bound taken from each problem's own levels on the oracle.
+    small: n <= 12 only and fewer draws (tests/golden/make_golden_fval_bound.py)."""
+    cases = []
+
+    def add(name, q, rng, base=None, keep=None):
+        lv, r = levels_of(ora, q, None if base is None else O.default_settings(**base))
+        if lv.size == 0:
+            return
+        for tag, b in bounds_from_levels(lv, rng):
+            if keep is None or tag.rstrip("0123456789") in keep:
+                cases.append((f"{name}_{tag}", q, dict(base or {}, fval_bound=b)))
+
+    for cfg, cnt in (("C3", 4),) if small else (("C1", 6), ("C3", 10)):
+        n, m, ms, na, seed, _ = O.CONFIGS[cfg]
+        for k in range(cnt):
+            add(f"{cfg}_{k:02d}", O.generate_qp(n, m, ms, na, rng=[seed, k]), np.random.default_rng([131, k]))
+    for trial in range(6 if small else 40):
+        rng = np.random.default_rng([132, trial])
+        eps = 10.0 ** rng.uniform(-10, -2)
+        n = int(rng.integers(4, 12)); m = int(rng.integers(n + 6, 3 * n + 2)); ms = int(rng.integers(0, min(n, m // 3) + 1))
+        na = int(rng.integers(2, min(n, m - ms)))
+        q = O.generate_nasty(n, m, ms, na, eps, rng, n_dup=int(rng.integers(0, 3)), n_eq=int(rng.integers(1, 3)), n_soft=int(rng.integers(1, 3)))
+        add(f"nasty_{trial:02d}", q, rng, keep=("mid", "at", "below") if small else None)
+    for k in range(4 if small else 16):      # the bound inside daqp_prox's inner daqp_ldp calls
+        rng = np.random.default_rng([133, k])
+        n = int(rng.integers(3, 13)); m = int(rng.integers(n + 2, 3 * n + 2)); ms = int(rng.integers(0, min(n, 4) + 1)) if k % 2 else 0
+        if k % 2:
+            q = O.generate_lp(n, m, ms, [134, k])
+        else:
+            q = O.generate_singular_qp(n, m, ms, rank=int(rng.integers(1, n)), rng=[135, k], kind="diag" if k % 4 == 2 else "dense")
+        add(("lp" if k % 2 else "singular") + f"_{k:02d}", q, rng, keep=("mid", "below", "none"))
+    return cases
+
+
+def fval_bound_warm_sequence(ora, mk_model, n=10, m=26, ms=3, na=5, seed=136):
+    """bound set (between two of the problem's levels) -> solve -> bound back to DAQP_INF -> solve again from the kept working set -> a
+    new f under a finite bound -> solve.  mk_model(n, m, ms, settings) gives the model to run it on; returns (inputs, [solve outputs])."""
+    q = O.generate_qp(n, m, ms, na, rng=[seed, 0])
+    lv, _ = levels_of(ora, q)
+    u = np.unique(lv)
+    assert u.size >= 3, u
+    b1 = 0.25 * (u[u.size // 2 - 1] + u[u.size // 2])
+    st = O.default_settings(fval_bound=b1)
+    mdl = mk_model(n, m, ms, st)
+    assert mdl.setup(q["H"], q["f"], q["A"], q["bupper"], q["blower"], None) >= 0
+    outs = [mdl.solve()]
+    if callable(mdl.settings):
+        mdl.settings(fval_bound=1e30)
+    else:
+        mdl.settings.fval_bound = 1e30       # the reference workspace borrows this struct
+    outs.append(mdl.solve())
+    f2 = q["f"] + 0.3 * np.random.default_rng([seed, 1]).standard_normal(n)
+    b3 = 0.5 * (outs[1][2] + 0.5 * float(np.sum(np.linalg.solve(q["H"], q["f"]) * q["f"]))) - 1e-3     # a little under the optimum's level of the old f
+    if callable(mdl.settings):
+        mdl.settings(fval_bound=b3)
+    else:
+        mdl.settings.fval_bound = b3
+    assert mdl.update(O.UPDATE_v, f=f2) == 0
+    outs.append(mdl.solve())
+    return dict(q, f2=f2, bounds=np.array([b1, 1e30, b3])), outs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-per-config", type=int, default=300)
@@ -339,6 +430,28 @@ def main():
                         print(f"MISMATCH update_mask n={n} trial {trial} mask {mask} step {step}: update {uo}/{ur} solve {ro[3]}/{ro[4]} vs {rr[3]}/{rr[4]}")
                 rm.close()
     print(f"  update masks: {mcount} update + solve steps")
+    # fval_bound (daqp.c:10,20): the dual-objective stop, bounds taken from each problem's own levels.  At this exit x, lam and fval
+    # are compared bit for bit as well (the iterate in LDP coordinates: api.c:27 skips ldp2qp_solution there)
+    stops = {}
+    for name, q, kw in fval_bound_cases(ora):
+        st = O.default_settings(**kw)
+        a = ora.quadprog(q["H"], q["f"], q["A"], q["bupper"], q["blower"], q.get("sense"), st)
+        b = strict.quadprog(q["H"], q["f"], q["A"], q["bupper"], q["blower"], q.get("sense"), st)
+        total += 1
+        if not (a[3] == b[3] and a[4] == b[4] and same(a[0], b[0]) and same(a[1], b[1]) and same(a[2], b[2])):
+            bad += 1
+            print(f"MISMATCH fval_bound {name}: oracle flag/iter {a[3]}/{a[4]} ref {b[3]}/{b[4]} dx {np.abs(a[0] - b[0]).max():.3e}")
+        tag = name.rsplit("_", 1)[1].rstrip("0123456789")
+        stops.setdefault(tag, []).append(b[3])
+    print("  fval_bound:", {t: f"{sum(1 for f_ in fl if f_ == -1)}/{len(fl)} stopped" for t, fl in stops.items()})
+    _, oa = fval_bound_warm_sequence(ora, lambda n, m, ms, st: ora.model(n, m, ms, settings=st))
+    _, ob = fval_bound_warm_sequence(ora, lambda n, m, ms, st: strict.model(n, m, ms, settings=st))
+    for t, (a, b) in enumerate(zip(oa, ob)):
+        total += 1
+        if not (a[3] == b[3] and a[4] == b[4] and same(a[0], b[0]) and same(a[1], b[1]) and same(a[2], b[2])):
+            bad += 1
+            print(f"MISMATCH fval_bound warm[{t}] {a[3]}/{a[4]} vs {b[3]}/{b[4]}")
+    print("  fval_bound warm sequence (bound, DAQP_INF, new f + bound): flag/iter", [(b[3], b[4]) for b in ob])
     print(f"pin result: {total - bad}/{total} bit-identical to the strict reference build")
     return 1 if bad else 0
 

@@ -64,6 +64,32 @@ def row_q(H, A, ms):
     return (Y * Y).sum(axis=0)
 
 
+def half_f_hinv_f(H, f):
+    """1/2 f'H^-1 f (longdouble): what the reported fval of a QP lacks of the least-distance problem's 1/2 (|u|^2 + soft slack), the
+    quantity DAQPSettings.fval_bound is compared with (daqp.c:10,20; api.c:471-477)"""
+    y = forward_solve(cholesky(H), np.array(f, dtype=LD).reshape(-1, 1))
+    return LD(0.5) * (y * y).sum()
+
+
+def dual_value(H, f, A, bupper, blower, sense, ms, lam, rho_soft, q=None):
+    """the dual function of the QP at multipliers lam (the problem's own units, the reference's sign convention), longdouble:
+        g(lam) = -1/2 (f + C'lam)' H^-1 (f + C'lam) - sum_k lam_k b_k - 1/2 rho_soft sum over soft rows of q_k lam_k^2
+    with b_k the upper bound where lam_k > 0 and the lower one where lam_k < 0.  A lower bound on the optimal value for every lam
+    (weak duality); at a dual-feasible iterate of the active-set method it equals that iterate's reported fval."""
+    f = np.array(f, dtype=LD).ravel()
+    n = f.size
+    lam = np.array(lam, dtype=LD).ravel()
+    bu, bl = np.array(bupper, dtype=LD).ravel(), np.array(blower, dtype=LD).ravel()
+    sense = np.zeros(lam.size, np.int64) if sense is None else np.asarray(sense, dtype=np.int64).ravel()
+    C = constraint_matrix(A, ms, n)
+    y = forward_solve(cholesky(H), (f + C.T @ lam).reshape(-1, 1))
+    b_side = np.where(lam > 0, bu, bl)
+    nz = lam != 0
+    soft = ((sense & SOFT) != 0) & nz
+    q = row_q(H, A, ms) if q is None else np.array(q, dtype=LD)
+    return -LD(0.5) * (y * y).sum() - (lam[nz] * b_side[nz]).sum() - LD(0.5) * LD(rho_soft) * (q * lam * lam)[soft].sum()
+
+
 def certificate(H, f, A, bupper, blower, sense, ms, x, lam, rho_soft, normalised=True, q=None, bar=1e-6):
     """dict of residuals of (x, lam) for the QP (H, f, A, bupper, blower, sense, ms); H=None: an LP.  q: row_q(H, A, ms) when the
     caller has it already (shared or unchanged matrices); bar: the slack beyond which a row with lam_k != 0 counts as inactive."""
