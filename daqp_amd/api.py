@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DAQPBatchProblem, DAQPBatchResult, DAQPProblem, DAQPResult, MEM_DEVICE, MEM_HOST,
+from ._lib import (DAQPBatchCertificate, DAQPBatchProblem, DAQPBatchResult, DAQPProblem, DAQPResult, MEM_DEVICE, MEM_HOST,
                    c_double_p, c_int_p, default_settings, lib)
 
 UPDATE_Rinv, UPDATE_M, UPDATE_v, UPDATE_d, UPDATE_sense = 1, 2, 4, 8, 16
@@ -369,6 +369,23 @@ class BatchModel:
         self._bw_keep = [keep, o]      # the launch reads / writes them after this call has returned
         return o
 
+    def certify(self, res, out=None):
+        """certify_batch on the inputs this model reads (the device tensors given to setup / setup_shared / update, kept in place)
+        and on res["x"], res["lam"] of a solve(): dict of the ten certificate arrays (daqp_certify_batch in include/daqp_amd.h).
+        out: 'torch' or 'numpy' (default: what res holds).  One kernel on the current stream; nothing of the batch's state is read, so
+        the call may come at any time after the solve.  A model set up from numpy arrays keeps no inputs: call certify_batch with them."""
+        k = self._keep
+        if "f" not in k or "bupper" not in k or "blower" not in k:
+            raise ValueError("BatchModel.certify needs the device tensors of setup(); this model was set up from host arrays: use certify_batch")
+        if out is None:
+            out = "torch" if _is_torch(res["x"]) else "numpy"
+        dev = k["f"].device
+        x = torch.as_tensor(res["x"], dtype=torch.float64, device=dev)
+        lam = torch.as_tensor(res["lam"], dtype=torch.float64, device=dev)
+        o, keep = _certify(k.get("H"), k["f"], k.get("A") if self.m > self.ms else None, k["bupper"], k["blower"], x, lam, k.get("sense"), self.ms, out)
+        self._cert_keep = keep      # the launch reads / writes them after this call has returned
+        return o
+
     def reset(self):
         """Every problem back to an empty working set (daqp_deactivate_constraints + reset_daqp_workspace per problem): the next
         solve is a cold one on the LDPs as they are; an update(f, bounds) not yet applied stays pending."""
@@ -482,6 +499,71 @@ def solve_batch(H, f, A, bupper, blower=None, sense=None, ms=None, out="numpy", 
     finally:
         bm.close()
     return res
+
+
+_CERT_REAL = ("stationarity", "stationarity_scale", "primal", "complementarity", "objective", "ray_residual", "ray_scale", "ray_support")
+_CERT_INT = ("wrong_sign", "primal_row")
+
+
+def _certify(H, f, A, bupper, blower, x, lam, sense, ms, out):
+    """(dict of outputs, what the launch still reads or writes)"""
+    if f.ndim != 2 or bupper.ndim != 2:
+        raise ValueError("f must be (N, n) and bupper (N, m)")
+    N, n, m = int(f.shape[0]), int(f.shape[1]), int(bupper.shape[1])
+    mA = 0 if A is None else int(A.shape[-2])
+    ms = m - mA if ms is None else int(ms)
+    if mA != m - ms or (A is not None and int(A.shape[-1]) != n):
+        raise ValueError("A must be (N, m - ms, n) or (m - ms, n)")
+    shared = (H is None or H.ndim == 2) and (A is None or A.ndim == 2) and not (H is None and A is None)
+    if not shared and ((H is not None and H.ndim != 3) or (A is not None and A.ndim != 3)):
+        raise ValueError("H and A are either both per problem (3-d) or both shared (2-d)")
+    for name, a, shape in (("H", H, (n, n) if shared else (N, n, n)), ("blower", blower, (N, m)), ("x", x, (N, n)), ("lam", lam, (N, m)),
+                           ("sense", sense, (N, m))):
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}")
+    keep, mems, ptrs = [], set(), []
+    for a, dt in ((H, np.float64), (f, np.float64), (A if mA else None, np.float64), (bupper, np.float64), (blower, np.float64),
+                  (sense, np.int32), (x, np.float64), (lam, np.float64)):
+        ptr, mem = _ptr(a, dt, keep)
+        ptrs.append(ptr)
+        if mem is not None:
+            mems.add(mem)
+    if len(mems) > 1:
+        raise ValueError("mix of host and device arrays in one call")
+    mem = mems.pop()
+    stream, device = None, -1
+    if mem == MEM_DEVICE:
+        dev = keep[0].device
+        device = dev.index
+        o = {k: torch.empty(N, dtype=torch.float64, device=dev) for k in _CERT_REAL}
+        o.update({k: torch.empty(N, dtype=torch.int32, device=dev) for k in _CERT_INT})
+        cert = DAQPBatchCertificate(*[o[k].data_ptr() for k in _CERT_REAL + _CERT_INT])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    else:
+        o = {k: np.empty(N) for k in _CERT_REAL}
+        o.update({k: np.empty(N, np.int32) for k in _CERT_INT})
+        cert = DAQPBatchCertificate(*[o[k].ctypes.data for k in _CERT_REAL + _CERT_INT])
+    p = DAQPBatchProblem(N, n, m, ms, *ptrs[:6], mem)
+    rc = lib().daqp_certify_batch(C.byref(cert), C.byref(p), ptrs[6], ptrs[7], 1 if shared else 0, device, stream)
+    if rc != 0:
+        raise RuntimeError(f"daqp_certify_batch failed ({rc}): {_lib.last_error()}")
+    if out == "torch":
+        o = {k: (v if _is_torch(v) else torch.from_numpy(v)) for k, v in o.items()}
+    else:
+        o = {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in o.items()}
+    return o, keep
+
+
+def certify_batch(H, f, A, bupper, blower, x, lam, sense=None, ms=None, out="numpy"):
+    """The certificate of N (x, lam) pairs, computed on the GPU in twice the working precision (daqp_certify_batch in
+    include/daqp_amd.h: definitions and the accuracy contract): dict of stationarity, stationarity_scale, primal, complementarity,
+    objective, ray_residual, ray_scale, ray_support (float64, N each) and wrong_sign, primal_row (int32, N each).  Stateless: it
+    certifies the answer of any solver.  numpy arrays (staged; the call waits) or device tensors (used in place; one kernel on the
+    current stream, nothing waits unless out='numpy').  f (N, n), bupper / blower / lam / sense (N, m), x (N, n); H (N, n, n) with
+    A (N, m - ms, n), or ONE H (n, n) with ONE A (m - ms, n) for all problems (shared structure); H=None: an LP.  A ray (ray_residual
+    == 0, ray_support < 0) with weight on a SOFT row proves nothing."""
+    o, _ = _certify(H, f, A, bupper, blower, x, lam, sense, ms, out)      # (out='numpy' has waited; a 'torch' result is ordered on the stream, and torch's allocator keeps freed inputs off other streams)
+    return o
 
 
 def minrep_batch(A, b, ms=None, out="numpy", info=None, device=None, **settings):

@@ -29,6 +29,7 @@
 #include "minrep.hip.h"
 #include "backward.hip.h"
 #include "nullspace.hip.h"
+#include "certify.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -2710,6 +2711,106 @@ int daqp_minrep_batch_info(float *setup_ms, float *solve_ms, unsigned long long 
     if (solve_ms) *solve_ms = g_minrep_ms[1];
     if (device_bytes) *device_bytes = g_minrep_bytes;
     return 0;
+}
+
+// ------------------------------------------------------------------------------------
+// daqp_certify_batch (include/daqp_amd.h, certify.hip.h): residuals and ray measures of (x, lam), stateless
+// ------------------------------------------------------------------------------------
+} // extern "C"
+namespace {
+struct CertStaging {      // device copies of host-resident arguments: gone when the call returns
+    std::vector<void *> bufs;
+    ~CertStaging() { for (void *p : bufs) (void)hipFree(p); }
+    template <typename T>
+    int in(const T **dev, const T *host, size_t count, hipStream_t s)
+    {
+        *dev = nullptr;
+        if (!host || count == 0) return 0;
+        T *d = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), count * sizeof(T)));
+        bufs.push_back(d);
+        HIPCHK(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, s));
+        *dev = d;
+        return 0;
+    }
+    template <typename T>
+    int out(T **dev, T *host, size_t count)
+    {
+        *dev = nullptr;
+        if (!host) return 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(dev), count * sizeof(T)));
+        bufs.push_back(*dev);
+        return 0;
+    }
+};
+int certify_launch(const CertifyArgs &a, hipStream_t s)
+{
+    if (a.n <= 64) {
+        hipLaunchKernelGGL(k_certify_wave<kCertWaves>, dim3((a.N + kCertWaves - 1) / kCertWaves), dim3(64 * kCertWaves), 0, s, a);
+    } else {
+        void (*k)(CertifyArgs) = a.n <= 128 ? k_certify_wg<2> : (a.n <= 256 ? k_certify_wg<4> : k_certify_wg<8>);
+        const size_t lds = certify_wg_lds_bytes(a.n);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(a.N), dim3(64 * kCertWaves), lds, s, a);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int certify_run(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_float *x, const c_float *lam, int shared, hipStream_t s)
+{
+    const size_t N = p->N, n = p->n, m = p->m, mA = p->m - p->ms, nm = shared ? 1 : N;
+    CertifyArgs a{};
+    a.N = p->N; a.n = p->n; a.m = p->m; a.ms = p->ms; a.shared = shared ? 1 : 0;
+    if (p->memory == DAQP_MEM_DEVICE) {
+        a.H = p->H; a.f = p->f; a.A = p->A; a.bupper = p->bupper; a.blower = p->blower; a.sense = p->sense; a.x = x; a.lam = lam;
+        a.stationarity = out->stationarity; a.stationarity_scale = out->stationarity_scale; a.primal = out->primal;
+        a.complementarity = out->complementarity; a.objective = out->objective; a.ray_residual = out->ray_residual;
+        a.ray_scale = out->ray_scale; a.ray_support = out->ray_support; a.wrong_sign = out->wrong_sign; a.primal_row = out->primal_row;
+        return certify_launch(a, s);
+    }
+    CertStaging st;
+    if (st.in(&a.H, p->H, nm * n * n, s) || st.in(&a.f, p->f, N * n, s) || st.in(&a.A, p->A, nm * mA * n, s) ||
+        st.in(&a.bupper, p->bupper, N * m, s) || st.in(&a.blower, p->blower, N * m, s) || st.in(&a.sense, p->sense, N * m, s) ||
+        st.in(&a.x, x, N * n, s) || st.in(&a.lam, lam, N * m, s))
+        return DAQP_EXIT_UNSUPPORTED;
+    double *const host_d[8] = {out->stationarity, out->stationarity_scale, out->primal, out->complementarity, out->objective,
+                               out->ray_residual, out->ray_scale, out->ray_support};
+    double **const dev_d[8] = {&a.stationarity, &a.stationarity_scale, &a.primal, &a.complementarity, &a.objective,
+                               &a.ray_residual, &a.ray_scale, &a.ray_support};
+    for (int i = 0; i < 8; ++i) if (st.out(dev_d[i], host_d[i], N)) return DAQP_EXIT_UNSUPPORTED;
+    if (st.out(&a.wrong_sign, out->wrong_sign, N) || st.out(&a.primal_row, out->primal_row, N)) return DAQP_EXIT_UNSUPPORTED;
+    if (certify_launch(a, s)) return DAQP_EXIT_UNSUPPORTED;
+    for (int i = 0; i < 8; ++i) if (host_d[i]) HIPCHK(hipMemcpyAsync(host_d[i], *dev_d[i], N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out->wrong_sign) HIPCHK(hipMemcpyAsync(out->wrong_sign, a.wrong_sign, N * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (out->primal_row) HIPCHK(hipMemcpyAsync(out->primal_row, a.primal_row, N * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+} // namespace
+extern "C" {
+
+int daqp_certify_batch(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_float *x, const c_float *lam, int shared, int device, void *hip_stream)
+{
+    if (!out || !p || !x || !lam) { set_err("daqp_certify_batch: null out, problem, x or lam"); return DAQP_EXIT_UNSUPPORTED; }
+    if (p->N <= 0 || p->n <= 0 || p->n > 511 || p->m < 0 || p->m > (1 << 24) || p->ms < 0 || p->ms > p->n || p->ms > p->m) {
+        set_err("daqp_certify_batch: bad dimensions N=%d n=%d m=%d ms=%d (N >= 1, 1 <= n <= 511, 0 <= m <= 2^24, ms <= n, ms <= m)", p->N, p->n, p->m, p->ms);
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (!p->f || (p->m > p->ms && !p->A) || (p->m > 0 && (!p->bupper || !p->blower))) {
+        set_err("daqp_certify_batch: null f, A or bounds");
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (p->memory != DAQP_MEM_HOST && p->memory != DAQP_MEM_DEVICE) { set_err("daqp_certify_batch: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_err("no HIP device: libdaqp_amd has no CPU path");
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    if (device >= ndev) { set_err("daqp_certify_batch: device %d of %d", device, ndev); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(device));
+    if (device < 64) g_devices_used.fetch_or(1ull << device);
+    return certify_run(out, p, x, lam, shared, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 // api.h: the reference's signature -- one polyhedron from host memory, default settings, the current device.  Without a device, or

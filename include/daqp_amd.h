@@ -394,6 +394,47 @@ int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c
  *   - batches created with ns_max > 0 are refused: q_k = c_k H^-1 c_k' of a soft row does not exist for a singular H. */
 int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status,
                                   int which, int memory);
+/* ---- the certificate of a batch of (x, lam) pairs: KKT residuals and Farkas measures, on the device, in twice the working precision
+ * (certify.hip.h).  Stateless: no DAQPBatch, no exit flags -- it reads the caller's H, f, A, bupper, blower, sense, x and lam and nothing
+ * else, so it certifies the answer of any solver and depends on no adopted pointer.  With C = [I_ms ; A] and the reference's sign
+ * convention (H x + f + C'lam = 0, lam_k > 0 on an upper bound), in the problem's own units (no row is scaled), per problem:
+ *   stationarity        max_j |(H x + f + C'lam)_j|
+ *   stationarity_scale  max(1, max_j |(H x)_j|, max_j |f_j|, max_j |(C'|lam|)_j|) with C'|lam| = sum_k c_kj |lam_k| (C keeps its signs);
+ *                       stationarity / stationarity_scale is the relative residual
+ *   primal              the largest of max(c_k x - bupper_k, blower_k - c_k x, 0) over the rows that are HELD: every row but the
+ *                       DAQP_IMMUTABLE ones that are no equality (bupper_k == blower_k), and the DAQP_SOFT ones with lam_k != 0
+ *   primal_row          the row where that maximum is reached (the first of equals); -1 when primal is 0 (or NaN)
+ *   complementarity     the largest of: for rows that are neither soft nor an equality and have lam_k != 0, the distance |c_k x - b_k| from
+ *                       the bound the sign of lam_k names; for equality rows (DAQP_IMMUTABLE, bupper_k == blower_k), |c_k x - bupper_k|
+ *   wrong_sign          the number of non-equality rows with lam_k != 0 whose nearer bound (c_k x - bupper_k >= blower_k - c_k x: the upper
+ *                       one) is not the one the sign of lam_k names
+ *   objective           1/2 x'Hx + f'x
+ *   ray_residual        max_j |(C'lam)_j|      ray_scale  max_j |(C'|lam|)_j|
+ *   ray_support         sum over lam_k > 0 of lam_k bupper_k  +  sum over lam_k < 0 of lam_k blower_k
+ * The last three read lam as a Farkas ray: for every feasible x, 0 = lam'Cx <= ray_support when C'lam = 0, so ray_residual == 0 together
+ * with ray_support < 0 proves {blower <= Cx <= bupper} empty.  DAQP_SOFT rows enter them as they are: a soft row may be violated, so A RAY
+ * WITH WEIGHT ON A SOFT ROW PROVES NOTHING.  Every quantity is computed for every problem; the caller reads the residuals of the OPTIMAL
+ * problems and the ray measures of the INFEASIBLE ones.
+ * Accuracy: every inner product and sum is accumulated as a (hi, lo) pair -- error-free products through fma, error-free sums, pairs
+ * across lanes and waves -- and rounded once.  For a quantity that is a sum of K terms with S = sum |terms|,
+ *       |computed - exact| <= 2^-52 |exact| + (K + 2)^2 2^-104 S
+ * (the bound of a compensated dot product, Ogita-Rump-Oishi 2005; derived in certify.hip.h, not measured); a max over rows or columns
+ * inherits the bound of its rows.  K: n + 1 + (m - ms) + 1 for a component of the stationarity residual, n for c_k x, n^2 + n for the
+ * objective, m for ray_support.  A NaN in x makes every output that depends on x NaN; non-finite inputs give non-finite outputs.
+ * Arguments: p->N problems of p->n variables and p->m rows, the first p->ms of them simple bounds; p->H == NULL: an LP (no H term);
+ * p->sense == NULL: all zero; shared != 0: p->H and p->A are ONE matrix each for all N problems (as daqp_batch_setup_shared takes
+ * them).  x is N*n, lam N*m.  p->memory applies to EVERY array -- the problem's, x, lam and the outputs: host arrays are staged and the
+ * call returns when the results are there; device arrays (on `device`; -1: the current one) are used in place and the call only
+ * enqueues one kernel on hip_stream (a hipStream_t; NULL: the null stream).  n <= 64 runs one wavefront per problem, n <= 511 one
+ * workgroup per problem.  Returns 0, or DAQP_EXIT_UNSUPPORTED with the reason in daqp_amd_last_error() and no device work: a NULL out,
+ * p, x or lam (or f, a needed A, bounds); N < 1, n outside 1..511, m outside 0..2^24, ms > n or ms > m; no HIP device. */
+typedef struct {
+    c_float *stationarity, *stationarity_scale, *primal, *complementarity, *objective,
+            *ray_residual, *ray_scale, *ray_support;   /* N each; any may be NULL */
+    int *wrong_sign, *primal_row;                       /* N each; any may be NULL */
+} DAQPBatchCertificate;
+int daqp_certify_batch(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_float *x, const c_float *lam,
+                       int shared /* p->H, p->A are one matrix each */, int device, void *hip_stream);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 
