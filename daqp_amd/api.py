@@ -386,6 +386,52 @@ class BatchModel:
         self._cert_keep = keep      # the launch reads / writes them after this call has returned
         return o
 
+    def refine(self, res, max_steps=3, out=None):
+        """Iterative refinement of res["x"], res["lam"] at the working set of the last solve() (daqp_batch_refine in
+        include/daqp_amd.h: the algebra, the merit and the acceptance rule): dict(x, lam, fval, status, steps, residual_before,
+        residual_after).  Works on copies: res itself is not modified.  status (N,) int32: 0, or why that problem was left as it came
+        in (its residuals are NaN, its fval is res["fval"] where res has one, NaN otherwise).  residual_after <= residual_before
+        for every problem with status 0.  out: 'torch' or 'numpy' (default: what res holds); device tensors stay on the device and
+        nothing waits for it.  Raises unless the last operation on the batch was a successful solve(), for a model created with
+        ns_max > 0 and for max_steps outside 1..8.  H, f, A and bounds given as device tensors must still be alive and unchanged."""
+        N, n, m = self.N, self.n, self.m
+        if out is None:
+            out = "torch" if _is_torch(res["x"]) else "numpy"
+        on_device = _is_torch(res["x"]) and res["x"].is_cuda
+        fv = res.get("fval") if hasattr(res, "get") else None
+        if on_device:
+            dev = res["x"].device
+            x = res["x"].to(torch.float64).contiguous().clone()
+            lam = torch.as_tensor(res["lam"], dtype=torch.float64, device=dev).contiguous().clone()
+            fval = torch.full((N,), float("nan"), dtype=torch.float64, device=dev) if fv is None else torch.as_tensor(fv, dtype=torch.float64, device=dev).contiguous().clone()
+            resid = torch.empty((N, 2), dtype=torch.float64, device=dev)
+            steps = torch.empty(N, dtype=torch.int32, device=dev)
+            status = torch.empty(N, dtype=torch.int32, device=dev)
+            ptrs = [t.data_ptr() for t in (x, lam, fval, resid, steps, status)]
+            mem = MEM_DEVICE
+        else:
+            host = lambda a: a.detach().cpu().numpy() if _is_torch(a) else a
+            x = np.array(host(res["x"]), dtype=np.float64, order="C")
+            lam = np.array(host(res["lam"]), dtype=np.float64, order="C")
+            fval = np.full(N, np.nan) if fv is None else np.array(host(fv), dtype=np.float64, order="C")
+            resid = np.empty((N, 2))
+            steps = np.empty(N, np.int32)
+            status = np.empty(N, np.int32)
+            ptrs = [a.ctypes.data for a in (x, lam, fval, resid, steps, status)]
+            mem = MEM_HOST
+        if tuple(x.shape) != (N, n) or tuple(lam.shape) != (N, m) or tuple(fval.shape) != (N,):
+            raise ValueError(f"res must hold x of shape {(N, n)} and lam of shape {(N, m)}")
+        rc = lib().daqp_batch_refine(self._h, *ptrs, int(max_steps), mem)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_refine failed ({rc}): {_lib.last_error()}")
+        o = dict(x=x, lam=lam, fval=fval, status=status, steps=steps, residual_before=resid[:, 0], residual_after=resid[:, 1])
+        self._rf_keep = o      # the launch reads / writes them after this call has returned
+        if out == "torch":
+            o = {k: (v if _is_torch(v) else torch.from_numpy(np.ascontiguousarray(v))) for k, v in o.items()}
+        else:
+            o = {k: (v.cpu().numpy() if _is_torch(v) else v) for k, v in o.items()}
+        return o
+
     def reset(self):
         """Every problem back to an empty working set (daqp_deactivate_constraints + reset_daqp_workspace per problem): the next
         solve is a cold one on the LDPs as they are; an update(f, bounds) not yet applied stays pending."""

@@ -30,6 +30,7 @@
 #include "backward.hip.h"
 #include "nullspace.hip.h"
 #include "certify.hip.h"
+#include "refine.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -246,6 +247,11 @@ struct DAQPBatch {
     int *bw_status = nullptr;
     double *bw_qsoft = nullptr, *bw_usoft = nullptr;   // the same for daqp_batch_backward_soft's extra outputs (each allocated when first asked for)
     int *bw_uid = nullptr;
+    // daqp_batch_refine (refine.hip.h): its own scratch and staging, so that a call leaves what daqp_batch_backward uses as it is
+    double *rf_scratch = nullptr;   // [rf_grid][refine_scratch_doubles]
+    int rf_grid = 0;
+    double *rf_x = nullptr, *rf_lam = nullptr, *rf_fval = nullptr, *rf_res = nullptr;   // staging of host-resident arguments
+    int *rf_steps = nullptr, *rf_status = nullptr;
 };
 
 namespace {
@@ -2103,6 +2109,77 @@ int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c
         else memset(qsoft, 0, bytes);
     }
     return rc;
+}
+
+// Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h, refine.hip.h): one launch on the batch's stream.
+// Refusals come before any device work.  Host-resident arguments go through staging buffers of the call's own and the call waits for
+// the results; device-resident ones are used in place and nothing waits.  Nothing of the batch's state is written.
+int daqp_batch_refine(DAQPBatch *b, c_float *x, c_float *lam, c_float *fval, c_float *residual, int *steps, int *status, int max_steps, int memory)
+{
+    if (!b || !x || !lam || !status) { set_err("daqp_batch_refine: null batch, x, lam or status"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->ns_max > 0) { set_err("daqp_batch_refine: batches created with ns_max > 0 (soft constraints) are not supported: soft rows change the (2,2) block of the system"); return DAQP_EXIT_UNSUPPORTED; }
+    if (max_steps < 1 || max_steps > kRefineMaxSteps) { set_err("daqp_batch_refine: max_steps must be in 1..%d (got %d)", kRefineMaxSteps, max_steps); return DAQP_EXIT_UNSUPPORTED; }
+    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_refine: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
+    if (!b->is_setup || !b->solved || b->pending_mask) {
+        set_err("daqp_batch_refine: the last operation on the batch was not a successful daqp_batch_solve");
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    const BatchDev &d = b->d;
+    if (!d.H || !d.f || !d.bu || !d.bl || (d.mA > 0 && !d.A)) { set_err("daqp_batch_refine: the batch has no H, f, A or bounds of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(b->device));
+    const size_t N = d.N, n = d.n, m = d.m;
+    // ---- which instantiation: the tiers of the adjoint kernel
+    const size_t lds_max = (size_t)144 * 1024;
+    const bool small = d.n <= 64 && refine_lds_bytes(d.n, d.cap, true, true) <= lds_max;
+    const size_t lds_nl = refine_lds_bytes(d.n, d.cap, small, true);
+    const bool nl = small || lds_nl <= lds_max;
+    const size_t lds = nl ? lds_nl : refine_lds_bytes(d.n, d.cap, false, false);
+    if (lds > lds_max) { set_err("daqp_batch_refine: n = %d with working sets of %d rows does not fit the refinement kernel", d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
+    void (*kr)(BatchDev, RefineArgs) = small ? k_refine<64, true, true> : (nl ? k_refine<256, false, true> : k_refine<256, false, false>);
+    RefineArgs a{};
+    a.max_steps = max_steps;
+    int grid = d.N;
+    if (!nl) {
+        a.scratch_per_wg = refine_scratch_doubles(d.n, d.cap);
+        if (!b->rf_scratch) {
+            // persistent workgroups, at most 512 of them and at most 256 MiB of scratch
+            size_t g = ((size_t)256 << 20) / (a.scratch_per_wg * sizeof(double));
+            if (g > 512) g = 512;
+            if (g < 16) g = 16;
+            if (g > N) g = N;
+            if (dev_alloc(b, &b->rf_scratch, g * a.scratch_per_wg)) return DAQP_EXIT_UNSUPPORTED;
+            b->rf_grid = (int)g;
+        }
+        a.scratch = b->rf_scratch;
+        grid = b->rf_grid;
+    }
+    if (memory == DAQP_MEM_DEVICE) {
+        a.x = x; a.lam = lam; a.fval = fval; a.residual = residual; a.steps = steps; a.status = status;
+    } else {
+        // each buffer when it is first needed: a failed allocation leaves the ones before it in place for the next call
+        if ((!b->rf_x && dev_alloc(b, &b->rf_x, N * n)) || (!b->rf_lam && dev_alloc(b, &b->rf_lam, N * m)) ||
+            (!b->rf_fval && dev_alloc(b, &b->rf_fval, N)) || (!b->rf_res && dev_alloc(b, &b->rf_res, 2 * N)) ||
+            (!b->rf_steps && dev_alloc(b, &b->rf_steps, N)) || (!b->rf_status && dev_alloc(b, &b->rf_status, N)))
+            return DAQP_EXIT_UNSUPPORTED;
+        HIPCHK(hipMemcpyAsync(b->rf_x, x, N * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (m) HIPCHK(hipMemcpyAsync(b->rf_lam, lam, N * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (fval) HIPCHK(hipMemcpyAsync(b->rf_fval, fval, N * sizeof(double), hipMemcpyHostToDevice, b->stream));      // (untouched where the status is not 0)
+        a.x = b->rf_x; a.lam = b->rf_lam; a.fval = fval ? b->rf_fval : nullptr; a.residual = residual ? b->rf_res : nullptr;
+        a.steps = steps ? b->rf_steps : nullptr; a.status = b->rf_status;
+    }
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kr, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
+    HIPCHK(hipGetLastError());
+    if (memory != DAQP_MEM_DEVICE) {
+        HIPCHK(hipMemcpyAsync(x, b->rf_x, N * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (m) HIPCHK(hipMemcpyAsync(lam, b->rf_lam, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (fval) HIPCHK(hipMemcpyAsync(fval, b->rf_fval, N * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (residual) HIPCHK(hipMemcpyAsync(residual, b->rf_res, 2 * N * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (steps) HIPCHK(hipMemcpyAsync(steps, b->rf_steps, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipMemcpyAsync(status, b->rf_status, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    }
+    return 0;
 }
 
 int daqp_batch_kernel_ms(DAQPBatch *b, float *setup_ms, float *solve_ms)

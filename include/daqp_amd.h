@@ -334,6 +334,45 @@ int daqp_batch_reset(DAQPBatch *b);
  *   - a pointer is NULL.
  * Not differentiated: lam, fval. */
 int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory);
+/* Fixed-precision iterative refinement of (x, lam) at the working set of the last daqp_batch_solve.  The solve works in the
+ * least-distance coordinates and transforms back through the computed R^-1, so its optimum carries an error of about
+ * cond(H) 2^-53; this call removes it.  Held fixed: the stored working set W (WS, n_active, the DAQP_LOWER bit of the workspace's
+ * sense), its rows C_W of C = [first ms rows of I; A] (unsigned) and b_W = bupper_k or blower_k by side.  x (N*n) and lam (N*m) come
+ * in as the caller has them -- normally what daqp_batch_solve returned, but any starting point is allowed, zeros included; lam is
+ * read on W only -- and go out refined.  One step:
+ *
+ *        r1 = -(H x + f + C_W' lam_W),  r2 = b_W - C_W x     in twice the working precision (error-free products, pairs summed,
+ *                                                            rounded once) on the caller's own H, f, A, bupper, blower: arrays
+ *                                                            adopted from device memory must still be valid and unchanged
+ *        [ H    C_W' ] [ dx   ]   [ r1 ]
+ *        [ C_W  0    ] [ dlam ] = [ r2 ]                     in fp64 on the kept factor of H, as daqp_batch_backward solves its system
+ *        x += dx,  lam_W += dlam
+ *
+ * Merit:  mu = max( |r1|_inf / max(1, |Hx|_inf, |f|_inf, |C_W'|lam_W||_inf),  max_k |r2_k| / max(1, |b_k|, sum_j |c_kj x_j|) ),
+ * the residuals in it being the doubled-precision ones.  A step is kept only if it lowers mu.  The loop ends at the first rejected
+ * step, at mu <= 2^-50, after a kept step that gained less than a factor 2, or after max_steps steps (1..8).  THE RETURNED PAIR NEVER
+ * HAS A LARGER mu THAN THE PAIR THAT CAME IN.
+ *   x, lam    N*n, N*m   in / out; lam off W is set to 0
+ *   fval      N          1/2 x'Hx + f'x of the returned x, formed as a pair and rounded once; may be NULL
+ *   residual  N*2        {mu of the pair that came in, mu of the pair that is returned}; may be NULL
+ *   steps     N          kept steps; may be NULL
+ *   status    N          0: done.  Otherwise the rules of daqp_batch_backward: the setup / update / exit flag of a problem that did not
+ *                        end DAQP_EXIT_OPTIMAL; DAQP_EXIT_UNSUPPORTED when it went through the proximal loop (the kept factor is that
+ *                        of H + eps I); DAQP_BACKWARD_SINGULAR when a pivot of the Gram matrix of the active rows falls below
+ *                        settings->zero_tol.  Such a problem's x and lam are left exactly as they came in, its steps are 0, both
+ *                        residuals NaN and its fval is not written.
+ * `memory` (DAQP_MEM_HOST / DAQP_MEM_DEVICE) applies to all six arrays.  The call runs on the batch's stream; with device memory it
+ * only enqueues (no host synchronisation), with host memory it returns when the results are there.  It reads the batch's state and
+ * writes none of it: a daqp_batch_backward, a daqp_batch_solve or an update followed by a warm solve return the same bits with the
+ * call and without it.  A batch set up with shared H and A is supported.
+ * Returns nonzero, with the reason in the last-error string and without any device work, when
+ *   - the last operation on the batch was not a successful daqp_batch_solve,
+ *   - the batch was created with ns_max > 0 (soft rows change the (2,2) block of the system),
+ *   - x, lam or status is NULL,
+ *   - max_steps is not in 1..8. */
+int daqp_batch_refine(DAQPBatch *b, c_float *x /* N*n, in/out */, c_float *lam /* N*m, in/out */,
+                      c_float *fval /* N, out, may be NULL */, c_float *residual /* N*2 out: before, after; may be NULL */,
+                      int *steps /* N, may be NULL */, int *status /* N */, int max_steps, int memory);
 /* The same adjoint for batches with soft rows (created with ns_max > 0; DAQP_SOFT in a row's sense).  An active soft row k is not
  * held at its bound b_k but at  c_k x - b_k = rho_soft q_k lam_k  with  q_k = c_k H^-1 c_k'  (the solver adds settings->rho_soft to
  * the diagonal of the NORMALISED M_W M_W'; lam is in the caller's units).  The optimum therefore solves
