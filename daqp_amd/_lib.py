@@ -82,7 +82,8 @@ EXPORTS = [
 # object was compiled with other flags)
 UNITS = {
     "daqp_amd.hip": ["daqp_amd.hip", "kernels.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h", "setup_fast.hip.h", "prox.hip.h",
-                     "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "backward.hip.h", "nullspace.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h", "certify.hip.h", "refine.hip.h"],
+                     "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h", "host.hip.h"],
+    "post_solve.hip": ["post_solve.hip", "host.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "reg_kernel.hip": ["reg_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "reg32_kernel.hip": ["reg32_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "wg_kernel.hip": ["wg_kernel.hip", "wg_kernel.hip.h", "wg_ldp.hip.h", "wg_layout.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h"],

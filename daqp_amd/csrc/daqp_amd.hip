@@ -11,9 +11,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <atomic>
-#include <vector>
-#include <string>
 #include <thread>
 
 #include "kernels.hip.h"
@@ -27,10 +24,7 @@
 #include "tiny_setup.hip.h"
 #include "setup_blk.hip.h"
 #include "minrep.hip.h"
-#include "backward.hip.h"
-#include "nullspace.hip.h"
-#include "certify.hip.h"
-#include "refine.hip.h"
+#include "host.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -78,14 +72,6 @@ extern template __global__ void k_ldp_wg<2, false>(BatchDev, int);
 extern template __global__ void k_ldp_wg<2, true>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, false>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, true>(BatchDev, int);
-// the adjoint kernel: backward_kernel.hip
-extern template __global__ void k_backward<64, true, true, false>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<256, false, true, false>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<256, false, false, false>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
-extern template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
 }
 
 using namespace daqp_amd;
@@ -95,21 +81,6 @@ namespace {
 thread_local char g_err[512] = "";
 thread_local float g_minrep_ms[2] = {0, 0};               // daqp_minrep_batch_info
 thread_local unsigned long long g_minrep_bytes = 0;
-void set_err(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return DAQP_EXIT_UNSUPPORTED;                                                     \
-        }                                                                                     \
-    } while (0)
 
 double now_s()
 {
@@ -126,145 +97,18 @@ void default_settings(DAQPSettings *s) // reference constants.h:15-29 / api.c:50
 
 } // namespace
 
-struct DAQPBatch {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    BatchDev d{};
-    std::vector<void *> owned;
-    unsigned long long bytes = 0;
-    // staging copies of host inputs (allocated on first use)
-    double *sH = nullptr, *sf = nullptr, *sA = nullptr, *sbu = nullptr, *sbl = nullptr;
-    int *ssense = nullptr;
-    size_t nH = 0, nf = 0, nA = 0, nbu = 0, nbl = 0, nsense = 0;   // elements each staging slot can hold
-    bool was_shared = false;   // last set up by daqp_batch_setup_shared: d.H / d.A are ONE matrix, not N
-    // library-owned result buffers
-    double *ox = nullptr, *olam = nullptr, *ofval = nullptr, *osoft = nullptr;
-    int *oflag = nullptr, *oiter = nullptr;
-    DAQPSettings *st_dev = nullptr;
-    BatchDev *d_dev = nullptr;
-    int C = 1;
-    bool spill = false;
-    int NB = 0, NP = 0;   // register-resident M variant (0: stream M from HBM)
-    bool tiny_setup = false;   // n <= 12, m <= 48: the 16-problems-per-wave setup kernel (tiny_setup.hip.h)
-    bool fast_setup = false, setup_spill = false;
-    bool fact_gs = false;           // 64 < n, factors that WOULD fit the LDS of k_setup: the default arithmetic's full setup still takes k_fact_wg + the scratch variant
-    double *fact_buf = nullptr;     // [N][4] records of k_fact_wg (setup_fact.hip.h), allocated for the shapes it serves
-    // workgroup-per-problem solve kernel (wg_kernel.hip.h): shapes without a register variant and more than 64 working-set rows
-    bool in_prox_loop = false;      // launches of the proximal outer loop (solve_with_prox)
-    bool use_wg = false;
-    int wg_W = 0, wg_C = 0, wg_grid = 0;
-    int wg_tier_grid = 0; size_t lds_wg_tier = 0;   // tiered launch of the workgroup kernel in front of a cold solve (0: none)
-    bool reg_handover = false;   // k_ldp_reg<2,32,*> may flag problems (more working-set rows than lanes: n = 64) for k_ldp right behind it
-    size_t lds_fb = 0;           // ... and that launch's LDS
-    bool img32 = false;          // default arithmetic: the solve launch is k_ldp_reg<NB, NP, true, 1> -- an fp32 image of M in the registers, two waves per
-                                 // SIMD, at most d.img_rows working-set rows -- with k_ldp_reg<NB, NP, true, 0> right behind it for the problems it flags
-    size_t lds_img = 0;          // ... and the image kernel's LDS
-    int img_kind = 0;            // its IMG template argument (2: the last row block split over two lanes per row; 1: full blocks)
-    // the carve-up of a WARM launch (daqp_update_ldp(UPDATE_v|UPDATE_d) fused into the solve: an MPC step starts from ~20 rows and moves a few): fewer
-    // rows held at all, so that at the same eight workgroups per CU more of them sit in LDS (the launch argument carries rows | cache, see k_ldp_reg)
-    int img_rows_warm = 0, img_cache_warm = 0;
-    size_t lds_img_warm = 0;
-    // hand-overs of the last solve launch, counted on the device and copied to pinned memory without waiting: when most of a batch goes to the
-    // full-register kernel anyway (working sets beyond what the image kernel holds), the next launches go there directly; every 16th tries again
-    int *img_ho_pin = nullptr;
-    unsigned img_skipped = 0;
-    bool img_only = false;       // no register shape holds M, but its fp32 image fits (k_ldp_reg<NB,NP,true,1> of kImgOnlyShapes, one wave per SIMD): default-mode solves run it in front of k_ldp
-    int io_nb = 0, io_np = 0;
-    int img_min_warm = 16384;
-    size_t lds_wg = 0;
-    double *wide_u = nullptr, *wide_l = nullptr;   // daqp_batch_setup_shared: +-1e30 bounds of the one factorisation
-    int *structural = nullptr, *shared_flag = nullptr;
-    bool exact_sticky = false;   // the sense of some working-set rows was replaced without the working set being rebuilt (a sense update without a
-                                 // sense array, utils.c:85-86; an update that took the new sense and then failed its bound check, utils.c:88-96): the
-                                 // reference iterates on from that state, and only its own arithmetic does the same (the default mode's carried
-                                 // intermediate results assume the flags they were formed with) -- solves use the exact kernels until the next update
-    int part_mask = 0;      // the last (re-)setup was a partial daqp_batch_update with this mask (k_setup<..., PART>): its regularising re-runs use the same kernel
-    int pending_mask = 0;   // daqp_batch_update(UPDATE_v|UPDATE_d) not yet applied: the next solve launch does it (k_ldp_reg mode 2)
-    size_t lds_setup = 0, lds_ldp = 0, lds_update = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool timed_setup = false, timed_solve = false;
-    bool is_setup = false;
-    // proximal outer loop (prox.hip.h): buffers appear with the first singular Hessian
-    ProxDev px{};
-    bool prox_ready = false;
-    int counter_host[4] = {0, 0, 0, 0};   // read-back of px.counter
-    // "is any Hessian singular?" after a setup: counted on the device, copied to pinned memory without waiting.  The next solve
-    // goes out FIRST (flagged problems sit it out), then the host looks at the count: no gap between the setup and the solve
-    // launch on the device.  Anything else that needs the final setup flags resolves the question first (resolve_setup).
-    int *pin_count = nullptr;
-    hipEvent_t ev_count = nullptr;
-    bool reg_pending = false;
-    int reg_mask = 0;
-    int n_prox_qps = 0;            // problems of the current setup that go through the outer loop
-    int prox_outer = 0;            // outer iterations of the last solve (the longest loop of the batch)
-    double *ident = nullptr;       // LP batches (H == NULL): the one n x n identity the setup pass reads as H
-    // single-problem workspaces: results of the last daqp_ldp, waiting for daqp_extract_result
-    // single-problem batches (N == 1, the daqp_quadprog / setup_daqp path): one pinned host slab and one device slab each for
-    // the inputs and the results (one copy each way instead of six), and the pool key of a parked batch
-    char *pin_in = nullptr, *dev_in = nullptr, *pin_out = nullptr;
-    size_t in_cap = 0, out_bytes = 0;
-    double *dev_mir = nullptr, *pin_mir = nullptr;   // host mirrors of a single-problem workspace: gathered slab (k_mirror) and its pinned landing zone
-    // One problem, latency: the result slab and the mirror slab are MAPPED host memory that the kernels write themselves, and the host
-    // learns that they are there from a mapped word written by a one-thread kernel at the end of the stream's work -- no hipMemcpy, no
-    // stream synchronisation on the way of daqp_quadprog / daqp_solve / daqp_update_ldp (0.34 / 0.14 ms per call were
-    // launches, small copies and synchronisations around ~0.1 ms / ~0.02 ms of kernels)
-    BatchDev d_pushed{};        // what d_dev holds (the register kernels read the descriptor through it): pushed again only when it differs
-    bool pushed_valid = false;
-    bool mapped_out = false, mapped_mir = false;     // ox .. oiter / dev_mir point into pin_out / pin_mir through their device addresses
-    int *pin_sig = nullptr, *pin_sig_dev = nullptr;  // the completion word and its device address
-    int sig_seq = 0;
-    bool lean = false;          // daqp_quadprog: no count of flagged Hessians, no activation launch (the solve launch activates; a flagged problem comes back with the internal code and takes the full path)
-    bool defer_wait = false;    // daqp_batch_solve only enqueues: the caller puts more work behind it, waits once and collects (daqp_ldp)
-    bool recheck_due = false;   // one problem: the second pass of an INFEASIBLE verdict is decided after the wait, on the host
-    char *pin_upd = nullptr, *pin_upd_dev = nullptr;  // f / bupper / blower of a deferred daqp_update_ldp(v|d): mapped, read by the solve launch in place
-    bool mirror_ldp_due = false;   // a deferred update's v / d have not reached the host mirrors yet: the next solve's gather brings them
-    hipEvent_t ev_in = nullptr;     // the last packed host->device copy (the pinned slab is free again once it has run)
-    std::string env_key;
-    int ns_max = 0;
-    unsigned long long *tstart = nullptr;   // [N] start stamps of the current daqp_batch_solve (allocated when a time limit is first armed)
-    std::vector<double> one_lam;
-    double one_fval = 0, one_soft = 0;
-    int one_flag = 0, one_iter = 0;
-    bool one_valid = false;   // one_* belong to the workspace's current LDP (cleared by setup / update / a failed solve)
-    // default arithmetic: INFEASIBLE verdicts of a solve straight after a setup are re-derived in the reference's arithmetic (recheck.hip.h)
-    bool fresh = false;        // the state is that of the last daqp_batch_setup (own H / A per problem, not an LP): nothing solved or updated since
-    int fresh_mask = 0;        // its init_mask
-    bool recheck = true;       // DAQP_AMD_NO_RECHECK=1 switches the second pass off
-    int recheck_device = -1;   // the same for inputs that were ADOPTED (DAQP_MEM_DEVICE: the second pass reads them again at solve time): -1 = not said
-                               // (on, unless DAQP_AMD_RECHECK_DEVICE=0), 0 / 1 = daqp_batch_set_recheck
-    bool inputs_adopted = false;   // the last setup's inputs were device arrays of the caller's, used in place
-    bool quiet_setup = false;  // the setup that runs now is the second pass of a one-problem batch: the caller's setup events stay as they are
-    hipEvent_t ev_r[2] = {nullptr, nullptr};   // around the second pass (daqp_batch_recheck_ms)
-    bool timed_recheck = false;
-    DAQPBatch *redo = nullptr; // companion batch in the exact mode (created with the first infeasible verdict, grown on demand)
-    int *redo_list = nullptr, *redo_count = nullptr, *pin_redo = nullptr, *pin_redo_dev = nullptr;   // pin_redo: a mapped host word the marking kernel writes
-    int rechecked = 0;         // problems the last solve sent through the second pass
-    // daqp_batch_backward (backward.hip.h)
-    bool solved = false;       // the last operation on the batch was a successful daqp_batch_solve: the stored iterate is that of the reported optimum
-    double *bw_scratch = nullptr;   // [bw_grid][backward_scratch_doubles]: rows and Gram matrix of shapes that LDS does not hold
-    int bw_grid = 0;
-    double *bw_g = nullptr, *bw_dz = nullptr, *bw_dbu = nullptr, *bw_dbl = nullptr;   // staging of host-resident arguments
-    int *bw_status = nullptr;
-    double *bw_qsoft = nullptr, *bw_usoft = nullptr;   // the same for daqp_batch_backward_soft's extra outputs (each allocated when first asked for)
-    int *bw_uid = nullptr;
-    // daqp_batch_refine (refine.hip.h): its own scratch and staging, so that a call leaves what daqp_batch_backward uses as it is
-    double *rf_scratch = nullptr;   // [rf_grid][refine_scratch_doubles]
-    int rf_grid = 0;
-    double *rf_x = nullptr, *rf_lam = nullptr, *rf_fval = nullptr, *rf_res = nullptr;   // staging of host-resident arguments
-    int *rf_steps = nullptr, *rf_status = nullptr;
-};
+// ---- what host.hip.h declares for the other host units
+void daqp_amd::set_err(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+std::atomic<unsigned long long> daqp_amd::g_devices_used{0};
+DAQPBatch::DAQPBatch() : px_own(new ProxDev{}, [](ProxDev *p) { delete p; }), px(*px_own) {}
 
 namespace {
-
-template <typename T>
-int dev_alloc(DAQPBatch *b, T **p, size_t count)
-{
-    if (count == 0) count = 1;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
-    b->owned.push_back(*p);
-    b->bytes += count * sizeof(T);
-    return 0;
-}
 
 __global__ void k_signal(int *host_word, int seq) { __hip_atomic_store(host_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
 // everything queued on the batch's stream so far has run when this returns: a one-thread kernel behind it writes the next sequence
@@ -879,7 +723,6 @@ namespace {
 // ~40 hipMalloc / hipFree and four events per call, an order of magnitude more than the solve itself.  A freed batch of ONE
 // problem is parked here instead and handed to the next create with the same shape, device and environment switches.
 std::mutex g_pool_mu;
-std::atomic<unsigned long long> g_devices_used{0};
 std::vector<DAQPBatch *> g_pool;
 constexpr size_t kPoolMax = 8;
 bool pool_enabled() { const char *e = getenv("DAQP_AMD_NO_POOL"); return !(e && atoi(e) != 0); }
@@ -1989,199 +1832,6 @@ int daqp_batch_working_sets(DAQPBatch *b, int *n_active_host, int *ws_host)
     return 0;
 }
 
-// The adjoint of the last solve (include/daqp_amd.h, backward.hip.h): one launch on the batch's stream.  Refusals come before any
-// device work.  Host-resident arguments go through the batch's own staging buffers and the call waits for the results; device-resident
-// ones are used in place and nothing waits.  Batches created with ns_max > 0 run the SOFT instantiations (soft rows in the (2,2)
-// block, q_k / u_k emitted where asked for); every other batch runs the kernels it ran before there were any.
-// nsw: the null-space kernel (nullspace.hip.h) on the same stream -- -1: not at all; 0: behind k_backward, for the problems that went
-// through the proximal loop only (it overwrites their outputs; every other problem keeps k_backward's bits); 1: instead of k_backward,
-// for every problem.  Launched for n <= 64 only: beyond, nsw == 0 leaves k_backward's DAQP_EXIT_UNSUPPORTED and nsw == 1 was refused.
-static int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
-                           c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory, int nsw = -1)
-{
-    if (!b->is_setup || !b->solved || b->pending_mask) {
-        set_err("%s: the last operation on the batch was not a successful daqp_batch_solve", who);
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    HIPCHK(hipSetDevice(b->device));
-    const BatchDev &d = b->d;
-    const size_t N = d.N, n = d.n, m = d.m, ns = b->ns_max;
-    const bool soft = b->ns_max > 0;
-    if (!soft) qsoft = nullptr, usoft = nullptr, usoft_id = nullptr;      // (ns_max == 0: usoft / usoft_id are empty, qsoft is zeroed below)
-    // ---- which instantiation: one wavefront with everything in LDS (n <= 64, and cap = n + ns_max + 1 rows and their Gram matrix
-    // fit), a workgroup with rows + Gram matrix in LDS, or in scratch
-    const size_t lds_max = (size_t)144 * 1024;
-    const bool small = d.n <= 64 && backward_lds_bytes(d.n, d.cap, true, true) <= lds_max;
-    const size_t lds_nl = backward_lds_bytes(d.n, d.cap, small, true);
-    const bool nl = small || lds_nl <= lds_max;
-    const size_t lds = nl ? lds_nl : backward_lds_bytes(d.n, d.cap, false, false);
-    if (lds > lds_max && nsw != 1) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
-    void (*kb)(BatchDev, BackwardArgs);
-    if (soft) kb = small ? k_backward<64, true, true, true> : (nl ? k_backward<256, false, true, true> : k_backward<256, false, false, true>);
-    else kb = small ? k_backward<64, true, true, false> : (nl ? k_backward<256, false, true, false> : k_backward<256, false, false, false>);
-    BackwardArgs a{};
-    int grid = d.N;
-    if (!nl && nsw != 1) {
-        a.scratch_per_wg = backward_scratch_doubles(d.n, d.cap);
-        if (!b->bw_scratch) {
-            // persistent workgroups, at most 512 of them and at most 256 MiB of scratch
-            size_t g = ((size_t)256 << 20) / (a.scratch_per_wg * sizeof(double));
-            if (g > 512) g = 512;
-            if (g < 16) g = 16;
-            if (g > N) g = N;
-            if (dev_alloc(b, &b->bw_scratch, g * a.scratch_per_wg)) return DAQP_EXIT_UNSUPPORTED;
-            b->bw_grid = (int)g;
-        }
-        a.scratch = b->bw_scratch;
-        grid = b->bw_grid;
-    }
-    if (memory == DAQP_MEM_DEVICE) {
-        a.grad_x = grad_x; a.dz = dz; a.dbupper = dbupper; a.dblower = dblower; a.status = status;
-        a.qsoft = qsoft; a.usoft = usoft; a.usoft_id = usoft_id;
-    } else {
-        if (!b->bw_status && (dev_alloc(b, &b->bw_g, N * n) || dev_alloc(b, &b->bw_dz, N * n) || dev_alloc(b, &b->bw_dbu, N * m) ||
-                         dev_alloc(b, &b->bw_dbl, N * m) || dev_alloc(b, &b->bw_status, N)))
-            return DAQP_EXIT_UNSUPPORTED;
-        if (qsoft && !b->bw_qsoft && dev_alloc(b, &b->bw_qsoft, N * m)) return DAQP_EXIT_UNSUPPORTED;
-        if (usoft && !b->bw_usoft && dev_alloc(b, &b->bw_usoft, N * ns * n)) return DAQP_EXIT_UNSUPPORTED;
-        if (usoft_id && !b->bw_uid && dev_alloc(b, &b->bw_uid, N * ns)) return DAQP_EXIT_UNSUPPORTED;
-        HIPCHK(hipMemcpyAsync(b->bw_g, grad_x, N * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        a.grad_x = b->bw_g; a.dz = b->bw_dz; a.dbupper = b->bw_dbu; a.dblower = b->bw_dbl; a.status = b->bw_status;
-        a.qsoft = qsoft ? b->bw_qsoft : nullptr; a.usoft = usoft ? b->bw_usoft : nullptr; a.usoft_id = usoft_id ? b->bw_uid : nullptr;
-    }
-    if (nsw != 1) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kb, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
-        HIPCHK(hipGetLastError());
-    }
-    if (nsw >= 0 && d.n <= 64) {
-        NullspaceArgs na{};
-        na.grad_x = a.grad_x; na.dz = a.dz; na.dbupper = a.dbupper; na.dblower = a.dblower; na.status = a.status;
-        na.lp = (b->ident && d.H == b->ident) ? 1 : 0;
-        na.only_prox = nsw == 0 ? 1 : 0;
-        const size_t lds_ns = nullspace_lds_bytes(d.n);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_backward_nullspace<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ns));
-        hipLaunchKernelGGL(k_backward_nullspace<64>, dim3(d.N), dim3(64), lds_ns, b->stream, d, na);
-        HIPCHK(hipGetLastError());
-    }
-    if (memory != DAQP_MEM_DEVICE) {
-        HIPCHK(hipMemcpyAsync(dz, b->bw_dz, N * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (m) HIPCHK(hipMemcpyAsync(dbupper, b->bw_dbu, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (m) HIPCHK(hipMemcpyAsync(dblower, b->bw_dbl, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (qsoft && m) HIPCHK(hipMemcpyAsync(qsoft, b->bw_qsoft, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (usoft) HIPCHK(hipMemcpyAsync(usoft, b->bw_usoft, N * ns * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (usoft_id) HIPCHK(hipMemcpyAsync(usoft_id, b->bw_uid, N * ns * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipMemcpyAsync(status, b->bw_status, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-    }
-    return 0;
-}
-
-int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory)
-{
-    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported: daqp_batch_backward_soft"); return DAQP_EXIT_UNSUPPORTED; }
-    return backward_launch("daqp_batch_backward", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory);
-}
-
-// The adjoint without a factor of H (nullspace.hip.h): which == 0 -- daqp_batch_backward, then the null-space kernel for the problems
-// that went through the proximal loop; which == 1 -- the null-space kernel for every problem.  It reads the caller's H and A in place.
-int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int which, int memory)
-{
-    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_nullspace: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_backward_nullspace: batches created with ns_max > 0 (soft constraints) are not supported: q_k = c_k H^-1 c_k' does not exist for a singular H"); return DAQP_EXIT_UNSUPPORTED; }
-    if (which != 0 && which != 1) { set_err("daqp_batch_backward_nullspace: which must be 0 (proximal problems only) or 1 (every problem)"); return DAQP_EXIT_UNSUPPORTED; }
-    if (which == 1 && b->d.n > 64) { set_err("daqp_batch_backward_nullspace: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", b->d.n); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->is_setup && b->d.H == nullptr) { set_err("daqp_batch_backward_nullspace: the batch has no Hessian of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
-    return backward_launch("daqp_batch_backward_nullspace", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory, which);
-}
-
-// The same for batches with soft rows (and, with identical results, for batches without): q_k, u_k and the ids of the SOFT rows of
-// each working set come back with the adjoint.  A batch with ns_max == 0 has none: its qsoft is zero, usoft / usoft_id are empty.
-int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
-                             c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory)
-{
-    if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_soft: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
-    const int rc = backward_launch("daqp_batch_backward_soft", b, grad_x, dz, dbupper, dblower, qsoft, usoft, usoft_id, status, memory);
-    if (rc == 0 && b->ns_max == 0 && qsoft && b->d.m) {      // no SOFT instantiation ran: no row of any working set is soft
-        const size_t bytes = sizeof(double) * (size_t)b->d.N * b->d.m;
-        if (memory == DAQP_MEM_DEVICE) HIPCHK(hipMemsetAsync(qsoft, 0, bytes, b->stream));
-        else memset(qsoft, 0, bytes);
-    }
-    return rc;
-}
-
-// Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h, refine.hip.h): one launch on the batch's stream.
-// Refusals come before any device work.  Host-resident arguments go through staging buffers of the call's own and the call waits for
-// the results; device-resident ones are used in place and nothing waits.  Nothing of the batch's state is written.
-int daqp_batch_refine(DAQPBatch *b, c_float *x, c_float *lam, c_float *fval, c_float *residual, int *steps, int *status, int max_steps, int memory)
-{
-    if (!b || !x || !lam || !status) { set_err("daqp_batch_refine: null batch, x, lam or status"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_refine: batches created with ns_max > 0 (soft constraints) are not supported: soft rows change the (2,2) block of the system"); return DAQP_EXIT_UNSUPPORTED; }
-    if (max_steps < 1 || max_steps > kRefineMaxSteps) { set_err("daqp_batch_refine: max_steps must be in 1..%d (got %d)", kRefineMaxSteps, max_steps); return DAQP_EXIT_UNSUPPORTED; }
-    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_refine: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
-    if (!b->is_setup || !b->solved || b->pending_mask) {
-        set_err("daqp_batch_refine: the last operation on the batch was not a successful daqp_batch_solve");
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    const BatchDev &d = b->d;
-    if (!d.H || !d.f || !d.bu || !d.bl || (d.mA > 0 && !d.A)) { set_err("daqp_batch_refine: the batch has no H, f, A or bounds of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(b->device));
-    const size_t N = d.N, n = d.n, m = d.m;
-    // ---- which instantiation: the tiers of the adjoint kernel
-    const size_t lds_max = (size_t)144 * 1024;
-    const bool small = d.n <= 64 && refine_lds_bytes(d.n, d.cap, true, true) <= lds_max;
-    const size_t lds_nl = refine_lds_bytes(d.n, d.cap, small, true);
-    const bool nl = small || lds_nl <= lds_max;
-    const size_t lds = nl ? lds_nl : refine_lds_bytes(d.n, d.cap, false, false);
-    if (lds > lds_max) { set_err("daqp_batch_refine: n = %d with working sets of %d rows does not fit the refinement kernel", d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
-    void (*kr)(BatchDev, RefineArgs) = small ? k_refine<64, true, true> : (nl ? k_refine<256, false, true> : k_refine<256, false, false>);
-    RefineArgs a{};
-    a.max_steps = max_steps;
-    int grid = d.N;
-    if (!nl) {
-        a.scratch_per_wg = refine_scratch_doubles(d.n, d.cap);
-        if (!b->rf_scratch) {
-            // persistent workgroups, at most 512 of them and at most 256 MiB of scratch
-            size_t g = ((size_t)256 << 20) / (a.scratch_per_wg * sizeof(double));
-            if (g > 512) g = 512;
-            if (g < 16) g = 16;
-            if (g > N) g = N;
-            if (dev_alloc(b, &b->rf_scratch, g * a.scratch_per_wg)) return DAQP_EXIT_UNSUPPORTED;
-            b->rf_grid = (int)g;
-        }
-        a.scratch = b->rf_scratch;
-        grid = b->rf_grid;
-    }
-    if (memory == DAQP_MEM_DEVICE) {
-        a.x = x; a.lam = lam; a.fval = fval; a.residual = residual; a.steps = steps; a.status = status;
-    } else {
-        // each buffer when it is first needed: a failed allocation leaves the ones before it in place for the next call
-        if ((!b->rf_x && dev_alloc(b, &b->rf_x, N * n)) || (!b->rf_lam && dev_alloc(b, &b->rf_lam, N * m)) ||
-            (!b->rf_fval && dev_alloc(b, &b->rf_fval, N)) || (!b->rf_res && dev_alloc(b, &b->rf_res, 2 * N)) ||
-            (!b->rf_steps && dev_alloc(b, &b->rf_steps, N)) || (!b->rf_status && dev_alloc(b, &b->rf_status, N)))
-            return DAQP_EXIT_UNSUPPORTED;
-        HIPCHK(hipMemcpyAsync(b->rf_x, x, N * n * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        if (m) HIPCHK(hipMemcpyAsync(b->rf_lam, lam, N * m * sizeof(double), hipMemcpyHostToDevice, b->stream));
-        if (fval) HIPCHK(hipMemcpyAsync(b->rf_fval, fval, N * sizeof(double), hipMemcpyHostToDevice, b->stream));      // (untouched where the status is not 0)
-        a.x = b->rf_x; a.lam = b->rf_lam; a.fval = fval ? b->rf_fval : nullptr; a.residual = residual ? b->rf_res : nullptr;
-        a.steps = steps ? b->rf_steps : nullptr; a.status = b->rf_status;
-    }
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kr, dim3(grid), dim3(small ? 64 : 256), lds, b->stream, d, a);
-    HIPCHK(hipGetLastError());
-    if (memory != DAQP_MEM_DEVICE) {
-        HIPCHK(hipMemcpyAsync(x, b->rf_x, N * n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (m) HIPCHK(hipMemcpyAsync(lam, b->rf_lam, N * m * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (fval) HIPCHK(hipMemcpyAsync(fval, b->rf_fval, N * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (residual) HIPCHK(hipMemcpyAsync(residual, b->rf_res, 2 * N * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (steps) HIPCHK(hipMemcpyAsync(steps, b->rf_steps, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipMemcpyAsync(status, b->rf_status, N * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-    }
-    return 0;
-}
-
 int daqp_batch_kernel_ms(DAQPBatch *b, float *setup_ms, float *solve_ms)
 {
     if (!b) return DAQP_EXIT_UNSUPPORTED;
@@ -2788,106 +2438,6 @@ int daqp_minrep_batch_info(float *setup_ms, float *solve_ms, unsigned long long 
     if (solve_ms) *solve_ms = g_minrep_ms[1];
     if (device_bytes) *device_bytes = g_minrep_bytes;
     return 0;
-}
-
-// ------------------------------------------------------------------------------------
-// daqp_certify_batch (include/daqp_amd.h, certify.hip.h): residuals and ray measures of (x, lam), stateless
-// ------------------------------------------------------------------------------------
-} // extern "C"
-namespace {
-struct CertStaging {      // device copies of host-resident arguments: gone when the call returns
-    std::vector<void *> bufs;
-    ~CertStaging() { for (void *p : bufs) (void)hipFree(p); }
-    template <typename T>
-    int in(const T **dev, const T *host, size_t count, hipStream_t s)
-    {
-        *dev = nullptr;
-        if (!host || count == 0) return 0;
-        T *d = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), count * sizeof(T)));
-        bufs.push_back(d);
-        HIPCHK(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, s));
-        *dev = d;
-        return 0;
-    }
-    template <typename T>
-    int out(T **dev, T *host, size_t count)
-    {
-        *dev = nullptr;
-        if (!host) return 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(dev), count * sizeof(T)));
-        bufs.push_back(*dev);
-        return 0;
-    }
-};
-int certify_launch(const CertifyArgs &a, hipStream_t s)
-{
-    if (a.n <= 64) {
-        hipLaunchKernelGGL(k_certify_wave<kCertWaves>, dim3((a.N + kCertWaves - 1) / kCertWaves), dim3(64 * kCertWaves), 0, s, a);
-    } else {
-        void (*k)(CertifyArgs) = a.n <= 128 ? k_certify_wg<2> : (a.n <= 256 ? k_certify_wg<4> : k_certify_wg<8>);
-        const size_t lds = certify_wg_lds_bytes(a.n);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k, dim3(a.N), dim3(64 * kCertWaves), lds, s, a);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int certify_run(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_float *x, const c_float *lam, int shared, hipStream_t s)
-{
-    const size_t N = p->N, n = p->n, m = p->m, mA = p->m - p->ms, nm = shared ? 1 : N;
-    CertifyArgs a{};
-    a.N = p->N; a.n = p->n; a.m = p->m; a.ms = p->ms; a.shared = shared ? 1 : 0;
-    if (p->memory == DAQP_MEM_DEVICE) {
-        a.H = p->H; a.f = p->f; a.A = p->A; a.bupper = p->bupper; a.blower = p->blower; a.sense = p->sense; a.x = x; a.lam = lam;
-        a.stationarity = out->stationarity; a.stationarity_scale = out->stationarity_scale; a.primal = out->primal;
-        a.complementarity = out->complementarity; a.objective = out->objective; a.ray_residual = out->ray_residual;
-        a.ray_scale = out->ray_scale; a.ray_support = out->ray_support; a.wrong_sign = out->wrong_sign; a.primal_row = out->primal_row;
-        return certify_launch(a, s);
-    }
-    CertStaging st;
-    if (st.in(&a.H, p->H, nm * n * n, s) || st.in(&a.f, p->f, N * n, s) || st.in(&a.A, p->A, nm * mA * n, s) ||
-        st.in(&a.bupper, p->bupper, N * m, s) || st.in(&a.blower, p->blower, N * m, s) || st.in(&a.sense, p->sense, N * m, s) ||
-        st.in(&a.x, x, N * n, s) || st.in(&a.lam, lam, N * m, s))
-        return DAQP_EXIT_UNSUPPORTED;
-    double *const host_d[8] = {out->stationarity, out->stationarity_scale, out->primal, out->complementarity, out->objective,
-                               out->ray_residual, out->ray_scale, out->ray_support};
-    double **const dev_d[8] = {&a.stationarity, &a.stationarity_scale, &a.primal, &a.complementarity, &a.objective,
-                               &a.ray_residual, &a.ray_scale, &a.ray_support};
-    for (int i = 0; i < 8; ++i) if (st.out(dev_d[i], host_d[i], N)) return DAQP_EXIT_UNSUPPORTED;
-    if (st.out(&a.wrong_sign, out->wrong_sign, N) || st.out(&a.primal_row, out->primal_row, N)) return DAQP_EXIT_UNSUPPORTED;
-    if (certify_launch(a, s)) return DAQP_EXIT_UNSUPPORTED;
-    for (int i = 0; i < 8; ++i) if (host_d[i]) HIPCHK(hipMemcpyAsync(host_d[i], *dev_d[i], N * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (out->wrong_sign) HIPCHK(hipMemcpyAsync(out->wrong_sign, a.wrong_sign, N * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (out->primal_row) HIPCHK(hipMemcpyAsync(out->primal_row, a.primal_row, N * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-}
-} // namespace
-extern "C" {
-
-int daqp_certify_batch(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_float *x, const c_float *lam, int shared, int device, void *hip_stream)
-{
-    if (!out || !p || !x || !lam) { set_err("daqp_certify_batch: null out, problem, x or lam"); return DAQP_EXIT_UNSUPPORTED; }
-    if (p->N <= 0 || p->n <= 0 || p->n > 511 || p->m < 0 || p->m > (1 << 24) || p->ms < 0 || p->ms > p->n || p->ms > p->m) {
-        set_err("daqp_certify_batch: bad dimensions N=%d n=%d m=%d ms=%d (N >= 1, 1 <= n <= 511, 0 <= m <= 2^24, ms <= n, ms <= m)", p->N, p->n, p->m, p->ms);
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    if (!p->f || (p->m > p->ms && !p->A) || (p->m > 0 && (!p->bupper || !p->blower))) {
-        set_err("daqp_certify_batch: null f, A or bounds");
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    if (p->memory != DAQP_MEM_HOST && p->memory != DAQP_MEM_DEVICE) { set_err("daqp_certify_batch: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_err("no HIP device: libdaqp_amd has no CPU path");
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= ndev) { set_err("daqp_certify_batch: device %d of %d", device, ndev); return DAQP_EXIT_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(device));
-    if (device < 64) g_devices_used.fetch_or(1ull << device);
-    return certify_run(out, p, x, lam, shared, reinterpret_cast<hipStream_t>(hip_stream));
 }
 
 // api.h: the reference's signature -- one polyhedron from host memory, default settings, the current device.  Without a device, or

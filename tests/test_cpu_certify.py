@@ -25,7 +25,7 @@ def test_entry_is_declared_exported_and_reachable():
     for word in ("stationarity_scale", "ray_support", "PROVES NOTHING", "(K + 2)^2 2^-104 S"):
         assert word in header, word
     assert "daqp_certify_batch" in _lib.EXPORTS and hasattr(daqp_amd.lib(), "daqp_certify_batch")
-    assert "certify_kernel.hip" in _lib.UNITS and "certify.hip.h" in _lib.UNITS["daqp_amd.hip"]
+    assert "certify_kernel.hip" in _lib.UNITS and "certify.hip.h" in _lib.UNITS["post_solve.hip"]
     assert callable(daqp_amd.certify_batch) and "certify_batch" in daqp_amd.__all__
     assert callable(daqp_amd.BatchModel.certify)
     assert [k for k, _ in _lib.DAQPBatchCertificate._fields_] == list(CC.REAL_KEYS + CC.INT_KEYS)
