@@ -73,7 +73,7 @@ EXPORTS = [
     "daqp_batch_device_bytes", "daqp_batch_rechecked", "daqp_batch_set_recheck", "daqp_batch_recheck_ms", "daqp_amd_last_error", "daqp_amd_device_count", "daqp_amd_version", "daqp_amd_has_tiny",
     "setup_daqp_ldp", "daqp_ldp", "ldp2qp_solution", "daqp_extract_result",
     "daqp_minrep_batch", "daqp_minrep_batch_info", "daqp_batch_reset", "reset_daqp_workspace", "daqp_deactivate_constraints",
-    "daqp_batch_backward", "daqp_batch_backward_soft", "daqp_batch_backward_nullspace", "daqp_certify_batch", "daqp_batch_refine",
+    "daqp_batch_backward", "daqp_batch_backward_soft", "daqp_batch_backward_nullspace", "daqp_certify_batch", "daqp_batch_refine", "daqp_batch_refine_nullspace",
     "daqp_batch_enable_trace", "daqp_batch_read_trace", "daqp_batch_enable_profile", "daqp_batch_read_profile", "daqp_batch_read_ldp",
 ]
 
@@ -83,13 +83,13 @@ EXPORTS = [
 UNITS = {
     "daqp_amd.hip": ["daqp_amd.hip", "kernels.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h", "setup_fast.hip.h", "prox.hip.h",
                      "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h", "host.hip.h"],
-    "post_solve.hip": ["post_solve.hip", "host.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
+    "post_solve.hip": ["post_solve.hip", "host.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "refine_nullspace.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "reg_kernel.hip": ["reg_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "reg32_kernel.hip": ["reg32_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "wg_kernel.hip": ["wg_kernel.hip", "wg_kernel.hip.h", "wg_ldp.hip.h", "wg_layout.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h"],
     "backward_kernel.hip": ["backward_kernel.hip", "backward.hip.h", "nullspace.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "certify_kernel.hip": ["certify_kernel.hip", "certify.hip.h"],
-    "refine_kernel.hip": ["refine_kernel.hip", "refine.hip.h", "certify.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
+    "refine_kernel.hip": ["refine_kernel.hip", "refine.hip.h", "refine_nullspace.hip.h", "nullspace.hip.h", "certify.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "setup_kernel.hip": ["setup_kernel.hip", "setup_blk.hip.h", "setup_fast.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "tiny_setup.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
 }
 HIPFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
@@ -315,6 +315,7 @@ def lib():
     L.daqp_batch_backward_nullspace.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci]
     L.daqp_certify_batch.argtypes = [C.POINTER(DAQPBatchCertificate), C.POINTER(DAQPBatchProblem), vp, vp, ci, ci, vp]
     L.daqp_batch_refine.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
+    L.daqp_batch_refine_nullspace.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci]
     L.reset_daqp_workspace.argtypes = [vp]
     L.reset_daqp_workspace.restype = None
     L.daqp_deactivate_constraints.argtypes = [vp]

@@ -386,15 +386,22 @@ class BatchModel:
         self._cert_keep = keep      # the launch reads / writes them after this call has returned
         return o
 
-    def refine(self, res, max_steps=3, out=None):
+    def refine(self, res, max_steps=3, out=None, nullspace=False):
         """Iterative refinement of res["x"], res["lam"] at the working set of the last solve() (daqp_batch_refine in
         include/daqp_amd.h: the algebra, the merit and the acceptance rule): dict(x, lam, fval, status, steps, residual_before,
         residual_after).  Works on copies: res itself is not modified.  status (N,) int32: 0, or why that problem was left as it came
         in (its residuals are NaN, its fval is res["fval"] where res has one, NaN otherwise).  residual_after <= residual_before
         for every problem with status 0.  out: 'torch' or 'numpy' (default: what res holds); device tensors stay on the device and
         nothing waits for it.  Raises unless the last operation on the batch was a successful solve(), for a model created with
-        ns_max > 0 and for max_steps outside 1..8.  H, f, A and bounds given as device tensors must still be alive and unchanged."""
+        ns_max > 0 and for max_steps outside 1..8.  H, f, A and bounds given as device tensors must still be alive and unchanged.
+
+        nullspace=True: daqp_batch_refine_nullspace with which = 0 -- problems that went through the proximal loop (singular H,
+        LPs; status -8 otherwise) are refined by the null-space kernel on the caller's own H, every other problem comes out bit
+        for bit as without it.  nullspace="all": which = 1, every problem through that kernel.  n <= 64 ("all" is refused beyond,
+        True leaves the -8).  A problem whose optimum is not locally unique (an LP off a vertex) has status -20."""
         N, n, m = self.N, self.n, self.m
+        if nullspace not in (False, True, "all"):
+            raise ValueError('nullspace must be False, True or "all"')
         if out is None:
             out = "torch" if _is_torch(res["x"]) else "numpy"
         on_device = _is_torch(res["x"]) and res["x"].is_cuda
@@ -421,9 +428,14 @@ class BatchModel:
             mem = MEM_HOST
         if tuple(x.shape) != (N, n) or tuple(lam.shape) != (N, m) or tuple(fval.shape) != (N,):
             raise ValueError(f"res must hold x of shape {(N, n)} and lam of shape {(N, m)}")
-        rc = lib().daqp_batch_refine(self._h, *ptrs, int(max_steps), mem)
+        if nullspace:
+            entry = "daqp_batch_refine_nullspace"
+            rc = lib().daqp_batch_refine_nullspace(self._h, *ptrs, int(max_steps), 1 if nullspace == "all" else 0, mem)
+        else:
+            entry = "daqp_batch_refine"
+            rc = lib().daqp_batch_refine(self._h, *ptrs, int(max_steps), mem)
         if rc != 0:
-            raise RuntimeError(f"daqp_batch_refine failed ({rc}): {_lib.last_error()}")
+            raise RuntimeError(f"{entry} failed ({rc}): {_lib.last_error()}")
         o = dict(x=x, lam=lam, fval=fval, status=status, steps=steps, residual_before=resid[:, 0], residual_after=resid[:, 1])
         self._rf_keep = o      # the launch reads / writes them after this call has returned
         if out == "torch":

@@ -1,6 +1,6 @@
 // post_solve.hip -- host side of the calls that run behind a solve: the adjoint (daqp_batch_backward*), the refinement
-// (daqp_batch_refine) and the certificate (daqp_certify_batch).  Each is argument checks, one or two launches and the three helpers
-// below; the kernels are in backward_kernel.hip, refine_kernel.hip and certify_kernel.hip.
+// (daqp_batch_refine, daqp_batch_refine_nullspace) and the certificate (daqp_certify_batch).  Each is argument checks, one or two
+// launches and the three helpers below; the kernels are in backward_kernel.hip, refine_kernel.hip and certify_kernel.hip.
 #include <cstring>
 
 #include "host.hip.h"
@@ -8,6 +8,7 @@
 #include "nullspace.hip.h"
 #include "certify.hip.h"
 #include "refine.hip.h"
+#include "refine_nullspace.hip.h"
 
 namespace daqp_amd {
 // the adjoint kernel: backward_kernel.hip
@@ -147,6 +148,61 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
     return st.finish();
 }
 
+// Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h, refine.hip.h): one launch on the batch's stream.
+// Refusals come before any device work.  Host-resident arguments go through the batch's own staging buffers and the call waits for
+// the results; device-resident ones are used in place and nothing waits.  Nothing of the batch's state is written.
+// nsw: the null-space kernel (refine_nullspace.hip.h) on the same stream -- -1: not at all; 0: behind k_refine, for the problems that
+// went through the proximal loop only (it overwrites their outputs; every other problem keeps k_refine's bits); 1: instead of
+// k_refine, for every problem.  Launched for n <= 64 only: beyond, nsw == 0 leaves k_refine's DAQP_EXIT_UNSUPPORTED and nsw == 1 was refused.
+int refine_launch(const char *who, DAQPBatch *b, c_float *x, c_float *lam, c_float *fval, c_float *residual, int *steps, int *status,
+                  int max_steps, int memory, int nsw = -1)
+{
+    if (!b || !x || !lam || !status) { set_err("%s: null batch, x, lam or status", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->ns_max > 0) { set_err("%s: batches created with ns_max > 0 (soft constraints) are not supported: soft rows change the (2,2) block of the system", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (max_steps < 1 || max_steps > kRefineMaxSteps) { set_err("%s: max_steps must be in 1..%d (got %d)", who, kRefineMaxSteps, max_steps); return DAQP_EXIT_UNSUPPORTED; }
+    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("%s: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (nsw == 1 && b->d.n > 64) { set_err("%s: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", who, b->d.n); return DAQP_EXIT_UNSUPPORTED; }
+    if (!b->is_setup || !b->solved || b->pending_mask) {
+        set_err("%s: the last operation on the batch was not a successful daqp_batch_solve", who);
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    const BatchDev &d = b->d;
+    if (!d.H || !d.f || !d.bu || !d.bl || (d.mA > 0 && !d.A)) { set_err("%s: the batch has no H, f, A or bounds of the caller's to read", who); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(b->device));
+    const size_t N = d.N, n = d.n, m = d.m;
+    const Tier t = pick_tier(d.n, d.cap, refine_lds_bytes);
+    if (!t.fits && nsw != 1) { set_err("%s: n = %d with working sets of %d rows does not fit the refinement kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
+    void (*kr)(BatchDev, RefineArgs) = t.small ? k_refine<64, true, true> : (t.nl ? k_refine<256, false, true> : k_refine<256, false, false>);
+    RefineArgs a{};
+    a.max_steps = max_steps;
+    int grid = d.N;
+    if (!t.nl && nsw != 1) {
+        a.scratch_per_wg = refine_scratch_doubles(d.n, d.cap);
+        if (!(grid = scratch_grid(b, b->refine, a.scratch_per_wg))) return DAQP_EXIT_UNSUPPORTED;
+        a.scratch = b->refine.scratch;
+    }
+    Staging st(b, b->refine.slot, b->stream, memory);
+    if (st.inout(&a.x, 0, x, N * n) || st.inout(&a.lam, 1, lam, N * m) || st.inout(&a.fval, 2, fval, N) ||      // (fval: untouched where the status is not 0)
+        st.out(&a.residual, 3, residual, 2 * N) || st.out(&a.steps, 4, steps, N) || st.out(&a.status, 5, status, N))
+        return DAQP_EXIT_UNSUPPORTED;
+    if (nsw != 1) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
+        hipLaunchKernelGGL(kr, dim3(grid), dim3(t.block), t.lds, b->stream, d, a);
+        HIPCHK(hipGetLastError());
+    }
+    if (nsw >= 0 && d.n <= 64) {
+        RefineNullspaceArgs na{};
+        na.r = a; na.r.scratch = nullptr; na.r.scratch_per_wg = 0;
+        na.lp = (b->ident && d.H == b->ident) ? 1 : 0;
+        na.only_prox = nsw == 0 ? 1 : 0;
+        const size_t lds_ns = nullspace_lds_bytes(d.n);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_refine_nullspace<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ns));
+        hipLaunchKernelGGL(k_refine_nullspace<64>, dim3(d.N), dim3(64), lds_ns, b->stream, d, na);
+        HIPCHK(hipGetLastError());
+    }
+    return st.finish();
+}
+
 int certify_launch(const CertifyArgs &a, hipStream_t s)
 {
     if (a.n <= 64) {
@@ -218,42 +274,20 @@ int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c
     return rc;
 }
 
-// Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h, refine.hip.h): one launch on the batch's stream.
-// Refusals come before any device work.  Host-resident arguments go through staging buffers of the call's own and the call waits for
-// the results; device-resident ones are used in place and nothing waits.  Nothing of the batch's state is written.
+// Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h): refine_launch above
 int daqp_batch_refine(DAQPBatch *b, c_float *x, c_float *lam, c_float *fval, c_float *residual, int *steps, int *status, int max_steps, int memory)
 {
-    if (!b || !x || !lam || !status) { set_err("daqp_batch_refine: null batch, x, lam or status"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_refine: batches created with ns_max > 0 (soft constraints) are not supported: soft rows change the (2,2) block of the system"); return DAQP_EXIT_UNSUPPORTED; }
-    if (max_steps < 1 || max_steps > kRefineMaxSteps) { set_err("daqp_batch_refine: max_steps must be in 1..%d (got %d)", kRefineMaxSteps, max_steps); return DAQP_EXIT_UNSUPPORTED; }
-    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_refine: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
-    if (!b->is_setup || !b->solved || b->pending_mask) {
-        set_err("daqp_batch_refine: the last operation on the batch was not a successful daqp_batch_solve");
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    const BatchDev &d = b->d;
-    if (!d.H || !d.f || !d.bu || !d.bl || (d.mA > 0 && !d.A)) { set_err("daqp_batch_refine: the batch has no H, f, A or bounds of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
-    HIPCHK(hipSetDevice(b->device));
-    const size_t N = d.N, n = d.n, m = d.m;
-    const Tier t = pick_tier(d.n, d.cap, refine_lds_bytes);
-    if (!t.fits) { set_err("daqp_batch_refine: n = %d with working sets of %d rows does not fit the refinement kernel", d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
-    void (*kr)(BatchDev, RefineArgs) = t.small ? k_refine<64, true, true> : (t.nl ? k_refine<256, false, true> : k_refine<256, false, false>);
-    RefineArgs a{};
-    a.max_steps = max_steps;
-    int grid = d.N;
-    if (!t.nl) {
-        a.scratch_per_wg = refine_scratch_doubles(d.n, d.cap);
-        if (!(grid = scratch_grid(b, b->refine, a.scratch_per_wg))) return DAQP_EXIT_UNSUPPORTED;
-        a.scratch = b->refine.scratch;
-    }
-    Staging st(b, b->refine.slot, b->stream, memory);
-    if (st.inout(&a.x, 0, x, N * n) || st.inout(&a.lam, 1, lam, N * m) || st.inout(&a.fval, 2, fval, N) ||      // (fval: untouched where the status is not 0)
-        st.out(&a.residual, 3, residual, 2 * N) || st.out(&a.steps, 4, steps, N) || st.out(&a.status, 5, status, N))
-        return DAQP_EXIT_UNSUPPORTED;
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
-    hipLaunchKernelGGL(kr, dim3(grid), dim3(t.block), t.lds, b->stream, d, a);
-    HIPCHK(hipGetLastError());
-    return st.finish();
+    return refine_launch("daqp_batch_refine", b, x, lam, fval, residual, steps, status, max_steps, memory);
+}
+
+// The refinement without a factor of H (refine_nullspace.hip.h): which == 0 -- daqp_batch_refine, then the null-space kernel for the
+// problems that went through the proximal loop; which == 1 -- the null-space kernel for every problem.  It reads the caller's H, f, A
+// and bounds in place.
+int daqp_batch_refine_nullspace(DAQPBatch *b, c_float *x, c_float *lam, c_float *fval, c_float *residual, int *steps, int *status,
+                                int max_steps, int which, int memory)
+{
+    if (which != 0 && which != 1) { set_err("daqp_batch_refine_nullspace: which must be 0 (proximal problems only) or 1 (every problem)"); return DAQP_EXIT_UNSUPPORTED; }
+    return refine_launch("daqp_batch_refine_nullspace", b, x, lam, fval, residual, steps, status, max_steps, memory, which);
 }
 
 // daqp_certify_batch (include/daqp_amd.h, certify.hip.h): residuals and ray measures of (x, lam), stateless

@@ -373,6 +373,40 @@ int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_floa
 int daqp_batch_refine(DAQPBatch *b, c_float *x /* N*n, in/out */, c_float *lam /* N*m, in/out */,
                       c_float *fval /* N, out, may be NULL */, c_float *residual /* N*2 out: before, after; may be NULL */,
                       int *steps /* N, may be NULL */, int *status /* N */, int max_steps, int memory);
+/* The same refinement WITHOUT a factor of H: the correction solved by the null-space method on the caller's own Hessian, for the
+ * problems that went through the proximal loop (singular H; an LP batch, H == NULL).  Their kept factor is that of H + eps I, so
+ * daqp_batch_refine answers DAQP_EXIT_UNSUPPORTED for them -- and they are the problems whose (x, lam) are limited by the outer
+ * fixed-point tolerance eta_prox / eps, not by the arithmetic.  The arrays, their in / out meaning, `memory`, the residuals in twice
+ * the working precision, the merit mu, the acceptance rule, the end conditions, max_steps in 1..8, lam off W set to 0 and fval as a
+ * pair rounded once are those of daqp_batch_refine: THE RETURNED PAIR NEVER HAS A LARGER mu THAN THE PAIR THAT CAME IN.  What differs
+ * is how the step is solved.  Per problem (one wavefront, fp64), once: the k = n_active rows of C_W scaled to unit length (norms s);
+ * Householder QR C_W' = Q [R; 0] without pivoting; Hr = Z'HZ with Z the last n - k columns of Q, Cholesky.  Then per step
+ *
+ *        y  = R^-T (r2 / s)
+ *        z  = Hr^-1 (Q'(r1 - H Q [y; 0]))[k:]                (n - k entries; none at a vertex)
+ *        dx = Q [y; z],   dlam = R^-1 (Q'(r1 - H dx))[:k] / s
+ *
+ *   which == 0   daqp_batch_refine's kernel runs first; the null-space kernel then runs on the same stream for the problems with
+ *                n_prox > 0 only and overwrites their outputs.  Every other problem comes out bit for bit as daqp_batch_refine
+ *                gives it.
+ *   which == 1   every problem goes through the null-space kernel: a second, independent algorithm for positive definite H.
+ *   status       the rules of daqp_batch_backward_nullspace: the setup / update / exit flag of a problem that did not end
+ *                DAQP_EXIT_OPTIMAL; DAQP_BACKWARD_SINGULAR when R_jj^2 < settings->zero_tol (dependent active rows; more than n rows
+ *                are dependent) or a pivot of Hr <= zero_tol max(1, max_i H_ii) (H not positive definite on the null space of C_W:
+ *                the optimum is not locally unique).  An LP has H = 0 -- the identity the batch stores for it is not H --: its
+ *                optimum must be a vertex (k == n), anything else is singular.  With a non-zero status x, lam and fval are left
+ *                exactly as they came in, steps is 0 and both residuals are NaN.
+ * The call runs on the batch's stream (two launches for which == 0); with device memory it only enqueues, with host memory it returns
+ * when the results are there.  It reads the batch's state and writes none of it.  H, f, A, bupper and blower are read where the last
+ * setup / update left them: device-resident inputs were adopted, not copied, so THEY MUST STILL BE VALID AND UNCHANGED AT THIS CALL.
+ * H is taken symmetric.  A batch set up with shared H and A is supported.
+ * Returns nonzero, with the reason in the last-error string and without any device work, in the cases of daqp_batch_refine (the last
+ * operation was not a successful daqp_batch_solve; ns_max > 0; x, lam or status NULL; max_steps not in 1..8), when which is neither
+ * 0 nor 1, and for which == 1 with n > 64: the kernel holds a problem in one wavefront.  With which == 0 the proximal problems of a
+ * batch with n > 64 keep DAQP_EXIT_UNSUPPORTED. */
+int daqp_batch_refine_nullspace(DAQPBatch *b, c_float *x /* N*n, in/out */, c_float *lam /* N*m, in/out */,
+                                c_float *fval /* N, out, may be NULL */, c_float *residual /* N*2 out: before, after; may be NULL */,
+                                int *steps /* N, may be NULL */, int *status /* N */, int max_steps, int which, int memory);
 /* The same adjoint for batches with soft rows (created with ns_max > 0; DAQP_SOFT in a row's sense).  An active soft row k is not
  * held at its bound b_k but at  c_k x - b_k = rho_soft q_k lam_k  with  q_k = c_k H^-1 c_k'  (the solver adds settings->rho_soft to
  * the diagonal of the NORMALISED M_W M_W'; lam is in the caller's units).  The optimum therefore solves
