@@ -5,7 +5,7 @@ reached only through the C ABI in include/daqp_amd.h.  This package is the host-
 the reference's Python binding for that path.
 """
 from ._lib import build, default_settings, last_error, lib, LIBPATH  # noqa: F401
-from .api import (BatchModel, MultiBatchModel, Model, certify_batch, minrep, minrep_batch, solve, solve_batch, solve_batch_multi, UPDATE_Rinv, UPDATE_M, UPDATE_v, UPDATE_d,  # noqa: F401
+from .api import (BatchModel, EliminatedBatchModel, MultiBatchModel, Model, certify_batch, minrep, minrep_batch, solve, solve_batch, solve_batch_multi, UPDATE_Rinv, UPDATE_M, UPDATE_v, UPDATE_d,  # noqa: F401
                   UPDATE_sense, UPDATE_unconstrained, UPDATE_eliminate)
 
 
@@ -19,4 +19,4 @@ def __getattr__(name):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["qp_layer", "build", "lib", "solve", "Model", "solve_batch", "solve_batch_multi", "minrep", "minrep_batch", "certify_batch", "BatchModel", "MultiBatchModel", "default_settings", "last_error"]
+__all__ = ["qp_layer", "build", "lib", "solve", "Model", "solve_batch", "solve_batch_multi", "minrep", "minrep_batch", "certify_batch", "BatchModel", "EliminatedBatchModel", "MultiBatchModel", "default_settings", "last_error"]

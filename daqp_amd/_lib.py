@@ -74,6 +74,8 @@ EXPORTS = [
     "setup_daqp_ldp", "daqp_ldp", "ldp2qp_solution", "daqp_extract_result",
     "daqp_minrep_batch", "daqp_minrep_batch_info", "daqp_batch_reset", "reset_daqp_workspace", "daqp_deactivate_constraints",
     "daqp_batch_backward", "daqp_batch_backward_soft", "daqp_batch_backward_nullspace", "daqp_certify_batch", "daqp_batch_refine", "daqp_batch_refine_nullspace",
+    "daqp_batch_eliminate", "daqp_batch_eliminate_update", "daqp_batch_elimination_problem", "daqp_batch_elimination_flags", "daqp_batch_expand",
+    "daqp_batch_elimination_basis", "daqp_batch_elimination_read", "daqp_batch_elimination_bytes", "daqp_batch_elimination_free",
     "daqp_batch_enable_trace", "daqp_batch_read_trace", "daqp_batch_enable_profile", "daqp_batch_read_profile", "daqp_batch_read_ldp",
 ]
 
@@ -83,7 +85,8 @@ EXPORTS = [
 UNITS = {
     "daqp_amd.hip": ["daqp_amd.hip", "kernels.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h", "setup_fast.hip.h", "prox.hip.h",
                      "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h", "host.hip.h"],
-    "post_solve.hip": ["post_solve.hip", "host.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "refine_nullspace.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
+    "post_solve.hip": ["post_solve.hip", "host.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "refine_nullspace.hip.h", "eliminate.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
+    "eliminate_kernel.hip": ["eliminate_kernel.hip", "eliminate.hip.h", "nullspace.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "reg_kernel.hip": ["reg_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "reg32_kernel.hip": ["reg32_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "wg_kernel.hip": ["wg_kernel.hip", "wg_kernel.hip.h", "wg_ldp.hip.h", "wg_layout.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h"],
@@ -316,6 +319,17 @@ def lib():
     L.daqp_certify_batch.argtypes = [C.POINTER(DAQPBatchCertificate), C.POINTER(DAQPBatchProblem), vp, vp, ci, ci, vp]
     L.daqp_batch_refine.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
     L.daqp_batch_refine_nullspace.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci]
+    L.daqp_batch_eliminate.argtypes = [C.POINTER(vp), C.POINTER(DAQPBatchProblem), c_int_p, ci, C.POINTER(DAQPSettings), ci, vp]
+    L.daqp_batch_eliminate_update.argtypes = [vp, vp, vp, vp, ci]
+    L.daqp_batch_elimination_problem.argtypes = [vp, C.POINTER(DAQPBatchProblem)]
+    L.daqp_batch_elimination_flags.argtypes = [vp, c_int_p]
+    L.daqp_batch_expand.argtypes = [vp, C.POINTER(DAQPBatchResult), C.POINTER(DAQPBatchResult)]
+    L.daqp_batch_elimination_basis.argtypes = [vp, vp, vp, vp, ci]
+    L.daqp_batch_elimination_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci]
+    L.daqp_batch_elimination_bytes.argtypes = [vp]
+    L.daqp_batch_elimination_bytes.restype = C.c_ulonglong
+    L.daqp_batch_elimination_free.argtypes = [vp]
+    L.daqp_batch_elimination_free.restype = None
     L.reset_daqp_workspace.argtypes = [vp]
     L.reset_daqp_workspace.restype = None
     L.daqp_deactivate_constraints.argtypes = [vp]

@@ -528,8 +528,205 @@ class BatchModel:
         return M, R, v, du, dl, sc
 
 
-def solve_batch(H, f, A, bupper, blower=None, sense=None, ms=None, out="numpy", **settings):
+class EliminatedBatchModel:
+    """N QPs of one shape whose equality rows are eliminated on the device before they are solved (daqp_batch_eliminate in
+    include/daqp_amd.h: the algebra): setup -> solve -> {update(f, bounds) -> solve}*, BatchModel's sequence and BatchModel's
+    result dict, in the caller's full space.  eq_rows: the equality rows of C = [first ms rows of I; A], ONE ascending set of
+    1 <= neq < n indices for the whole batch; bupper == blower is expected there.  The model owns the elimination handle and an
+    inner BatchModel of the reduced shape (n - neq, m - neq, 0), exposed as .reduced (its working sets, prox_info, kernel_ms).
+    .flags (N,) int32 after setup / update: 1, -6 (dependent equality rows) or -8 (bupper != blower on an equality row); such a
+    problem comes back with that exit flag and zero x, lam -- the rest of the batch is untouched.  Inputs are numpy arrays (copied) or
+    device tensors (used in place: they must stay alive and unchanged while the model is in use -- expansion reads H, f and A).
+    settings: a dict of DAQP settings.  backward / refine / qp_layer do not go through an eliminated model: basis() gives x0, Z, c0."""
+
+    def __init__(self, N, n, m, ms, eq_rows, ns_max=0, settings=None, device=None):
+        self.N, self.n, self.m, self.ms, self.ns = N, n, m, ms, ns_max
+        self.eq_rows = np.ascontiguousarray(eq_rows, dtype=np.int32).ravel()
+        neq = self.neq = int(self.eq_rows.size)
+        if not 1 <= neq < n:
+            raise ValueError(f"eq_rows must name 1 .. n-1 rows (got {neq}, n = {n})")
+        if (self.eq_rows < 0).any() or (self.eq_rows >= m).any() or (np.diff(self.eq_rows) <= 0).any():
+            raise ValueError("eq_rows must be distinct, ascending indices into 0..m-1")
+        self.nr, self.mr = n - neq, m - neq
+        self.kept_rows = np.setdiff1d(np.arange(m, dtype=np.int32), self.eq_rows)
+        self._settings = default_settings(**(settings or {}))
+        self.reduced = BatchModel(N, self.nr, self.mr, 0, ns_max, device=device, **(settings or {}))
+        self.device = self.reduced.device
+        # ONE stream for the handle and the reduced batch, taken here: eliminate / update / expand only enqueue with device-resident arrays,
+        # and the reduced setup, update and solve are ordered against them by sitting on the same stream
+        self._stream = None
+        if torch is not None and torch.cuda.is_available():
+            self._stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            lib().daqp_batch_set_stream(self.reduced._h, self._stream)
+        self._el = None
+        self._full = {}
+        self._rp = None
+        self.flags = None
+
+    def close(self):
+        if getattr(self, "_el", None):
+            lib().daqp_batch_elimination_free(self._el)
+            self._el = None
+        if getattr(self, "reduced", None) is not None:
+            self.reduced.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _pointers(arrays):
+        """pointers and the one memory side of (name, array, dtype) triples; what must stay referenced comes back by name"""
+        keep, ptrs, mems = {}, [], set()
+        for name, a, dt in arrays:
+            tmp = []
+            p, mem = _ptr(a, dt, tmp)
+            ptrs.append(p)
+            if mem is not None:
+                mems.add(mem)
+                keep[name] = tmp[0]
+        if len(mems) > 1:
+            raise ValueError("mix of host and device arrays in one call")
+        return ptrs, (mems.pop() if mems else MEM_HOST), keep
+
+    def _read_flags(self):
+        fl = np.zeros(self.N, np.int32)
+        rc = lib().daqp_batch_elimination_flags(self._el, _ip(fl))
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_elimination_flags failed ({rc}): {_lib.last_error()}")
+        self.flags = fl
+
+    def setup(self, H, f, A, bupper, blower, sense=None, init_mask=0):
+        self.eliminate(H, f, A, bupper, blower, sense)
+        self.setup_reduced(init_mask)
+        self._read_flags()
+        return self
+
+    def eliminate(self, H, f, A, bupper, blower, sense=None):
+        """the first half of setup(): daqp_batch_eliminate alone (a new handle; follow with setup_reduced)"""
+        ptrs, mem, keep = self._pointers((("H", H, np.float64), ("f", f, np.float64), ("A", A if self.m > self.ms else None, np.float64),
+                                          ("bupper", bupper, np.float64), ("blower", blower, np.float64), ("sense", sense, np.int32)))
+        p = DAQPBatchProblem(self.N, self.n, self.m, self.ms, *ptrs, mem)
+        if self._el:
+            lib().daqp_batch_elimination_free(self._el)
+            self._el = None
+        stream, dev = self._stream, -1 if self.device is None else int(self.device)
+        h = C.c_void_p()
+        rc = lib().daqp_batch_eliminate(C.byref(h), C.byref(p), _ip(self.eq_rows), self.neq, C.byref(self._settings), dev, stream)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_eliminate failed ({rc}): {_lib.last_error()}")
+        self._el = h
+        self._full = keep
+        self._rp = DAQPBatchProblem()
+        rc = lib().daqp_batch_elimination_problem(self._el, C.byref(self._rp))
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_elimination_problem failed ({rc}): {_lib.last_error()}")
+
+    def setup_reduced(self, init_mask=0):
+        """the second half of setup(): daqp_batch_setup of the inner model on the handle's reduced arrays"""
+        rc = lib().daqp_batch_setup(self.reduced._h, C.byref(self._rp), init_mask)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_setup of the reduced batch failed ({rc}): {_lib.last_error()}")
+
+    def update(self, f=None, bupper=None, blower=None, **other):
+        """new f and / or bounds on the kept factor of the equality rows and the kept factors and working sets of the reduced batch:
+        the warm path.  Anything else (H, A, sense) changes the factor: call setup."""
+        if any(v is not None for v in other.values()):
+            raise ValueError(f"EliminatedBatchModel.update takes f, bupper and blower only; for {sorted(other)} call setup again")
+        if not self._el:
+            raise RuntimeError("EliminatedBatchModel.update called before setup")
+        ptrs, mem, keep = self._pointers((("f", f, np.float64), ("bupper", bupper, np.float64), ("blower", blower, np.float64)))
+        rc = lib().daqp_batch_eliminate_update(self._el, *ptrs, mem)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_eliminate_update failed ({rc}): {_lib.last_error()}")
+        self._full.update(keep)
+        mask = UPDATE_v | (UPDATE_d if (bupper is not None or blower is not None) else 0)      # (new bounds move x0, and with it f_r)
+        rc = lib().daqp_batch_update(self.reduced._h, mask, C.byref(self._rp))
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_update of the reduced batch failed ({rc}): {_lib.last_error()}")
+        self._read_flags()
+        return self
+
+    def solve(self, out="numpy"):
+        """dict(x, lam, fval, exitflag, iter, soft_slack) in the full space: the keys and shapes of BatchModel.solve"""
+        if not self._el:
+            raise RuntimeError("EliminatedBatchModel.solve called before setup")
+        return self.expand(self.reduced.solve(out=out), out)
+
+    def expand(self, r, out="numpy"):
+        """the second half of solve(): daqp_batch_expand of a result dict of .reduced.solve(out=out)"""
+        N, n, m = self.N, self.n, self.m
+        if out == "torch":
+            dev = torch.device("cuda", self.device)
+            o = dict(x=torch.empty((N, n), dtype=torch.float64, device=dev), lam=torch.empty((N, m), dtype=torch.float64, device=dev),
+                     fval=torch.empty(N, dtype=torch.float64, device=dev), soft_slack=torch.empty(N, dtype=torch.float64, device=dev),
+                     exitflag=torch.empty(N, dtype=torch.int32, device=dev), iter=torch.empty(N, dtype=torch.int32, device=dev))
+            ptr, mem = (lambda t: t.data_ptr()), MEM_DEVICE
+        else:
+            o = dict(x=np.empty((N, n)), lam=np.empty((N, m)), fval=np.empty(N), soft_slack=np.empty(N),
+                     exitflag=np.empty(N, np.int32), iter=np.empty(N, np.int32))
+            ptr, mem = (lambda a: a.ctypes.data), MEM_HOST
+        keys = ("x", "lam", "fval", "soft_slack", "exitflag", "iter")
+        rr = DAQPBatchResult(*[ptr(r[k]) for k in keys], mem, 0, 0)
+        fr = DAQPBatchResult(*[ptr(o[k]) for k in keys], mem, 0, 0)
+        rc = lib().daqp_batch_expand(self._el, C.byref(rr), C.byref(fr))
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_expand failed ({rc}): {_lib.last_error()}")
+        self._out_keep = [r, o]
+        return o
+
+    def reset(self):
+        """the reduced batch back to empty working sets: the next solve is a cold one"""
+        self.reduced.reset()
+        return self
+
+    def certify(self, res, out=None):
+        """certify_batch on the caller's FULL problem and res["x"], res["lam"] of a solve()"""
+        k = self._full
+        if out is None:
+            out = "torch" if _is_torch(res["x"]) else "numpy"
+        x, lam = res["x"], res["lam"]
+        if _is_torch(k["f"]) and k["f"].is_cuda:
+            x = torch.as_tensor(x, dtype=torch.float64, device=k["f"].device)
+            lam = torch.as_tensor(lam, dtype=torch.float64, device=k["f"].device)
+        else:
+            x = x.detach().cpu().numpy() if _is_torch(x) else x
+            lam = lam.detach().cpu().numpy() if _is_torch(lam) else lam
+        o, keep = _certify(k.get("H"), k["f"], k.get("A"), k["bupper"], k["blower"], x, lam, k.get("sense"), self.ms, out)
+        self._cert_keep = keep
+        return o
+
+    def basis(self):
+        """dict(x0 (N, n), Z (N, n, n - neq), c0 (N,)) as numpy arrays: x = x0 + Z y, fval = fval_r + c0"""
+        if not self._el:
+            raise RuntimeError("EliminatedBatchModel.basis called before setup")
+        o = dict(x0=np.empty((self.N, self.n)), Z=np.empty((self.N, self.n, self.nr)), c0=np.empty(self.N))
+        rc = lib().daqp_batch_elimination_basis(self._el, o["x0"].ctypes.data, o["Z"].ctypes.data, o["c0"].ctypes.data, MEM_HOST)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_elimination_basis failed ({rc}): {_lib.last_error()}")
+        return o
+
+    def reduced_problem(self):
+        """the reduced arrays as numpy copies (daqp_batch_elimination_read): dict(H (None for an LP), f, A, bupper, blower, sense)"""
+        if not self._el:
+            raise RuntimeError("EliminatedBatchModel.reduced_problem called before setup")
+        N, nr, mr = self.N, self.nr, self.mr
+        o = dict(H=None if not self._rp.H else np.empty((N, nr, nr)), f=np.empty((N, nr)), A=np.empty((N, mr, nr)), bupper=np.empty((N, mr)),
+                 blower=np.empty((N, mr)), sense=np.empty((N, mr), np.int32))
+        rc = lib().daqp_batch_elimination_read(self._el, *[None if o[k] is None else o[k].ctypes.data for k in ("H", "f", "A", "bupper", "blower", "sense")], MEM_HOST)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_elimination_read failed ({rc}): {_lib.last_error()}")
+        return o
+
+    def device_bytes(self):
+        return int(lib().daqp_batch_elimination_bytes(self._el)) + self.reduced.device_bytes()
+
+
+def solve_batch(H, f, A, bupper, blower=None, sense=None, ms=None, out="numpy", eq_rows=None, **settings):
     """N x daqp_quadprog in one call (daqp_quadprog_batch semantics: unconstrained shortcut on).
+    eq_rows: a list or array of equality rows (one set for the batch) sends the call through EliminatedBatchModel.
 
     Returns dict(x, lam, fval, exitflag, iter, soft_slack)."""
     N, n = f.shape[0], f.shape[1]
@@ -538,6 +735,20 @@ def solve_batch(H, f, A, bupper, blower=None, sense=None, ms=None, out="numpy", 
     ms = m - mA if ms is None else ms
     if blower is None:
         blower = (torch.full_like(bupper, -INF) if _is_torch(bupper) else np.full(bupper.shape, -INF))
+    if eq_rows is not None and N > 0:
+        ns = 0
+        if sense is not None:
+            s = sense.cpu().numpy() if _is_torch(sense) else np.asarray(sense)
+            ns = int(((s & 8) != 0).sum(axis=1).max()) if s.size else 0
+        em = EliminatedBatchModel(N, n, m, ms, eq_rows, ns, settings=settings)
+        try:
+            em.setup(H, f, A, bupper, blower, sense, init_mask=UPDATE_unconstrained | UPDATE_eliminate)
+            res = em.solve(out=out)
+            if out == "torch":
+                torch.cuda.synchronize()
+        finally:
+            em.close()
+        return res
     if N == 0:   # an empty batch is a valid (empty) answer, as it is for daqp_quadprog_batch
         if out == "torch" and _is_torch(f):
             z = lambda *sh, dt=torch.float64: torch.zeros(sh, dtype=dt, device=f.device)

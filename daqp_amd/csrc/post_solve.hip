@@ -9,6 +9,7 @@
 #include "certify.hip.h"
 #include "refine.hip.h"
 #include "refine_nullspace.hip.h"
+#include "eliminate.hip.h"
 
 namespace daqp_amd {
 // the adjoint kernel: backward_kernel.hip
@@ -19,7 +20,36 @@ extern template __global__ void k_backward<64, true, true, true>(BatchDev, Backw
 extern template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
+// the elimination kernels: eliminate_kernel.hip
+extern template __global__ void k_eliminate<1, 1>(ElimDev);
+extern template __global__ void k_eliminate<2, 4>(ElimDev);
+extern template __global__ void k_eliminate<4, 4>(ElimDev);
+extern template __global__ void k_eliminate<8, 4>(ElimDev);
+extern template __global__ void k_eliminate_update<1>(ElimDev);
+extern template __global__ void k_eliminate_update<2>(ElimDev);
+extern template __global__ void k_eliminate_update<4>(ElimDev);
+extern template __global__ void k_eliminate_update<8>(ElimDev);
+extern template __global__ void k_expand<1>(ElimDev, ExpandArgs);
+extern template __global__ void k_expand<2>(ElimDev, ExpandArgs);
+extern template __global__ void k_expand<4>(ElimDev, ExpandArgs);
+extern template __global__ void k_expand<8>(ElimDev, ExpandArgs);
+extern template __global__ void k_elim_basis<1>(ElimDev, double *);
+extern template __global__ void k_elim_basis<2>(ElimDev, double *);
+extern template __global__ void k_elim_basis<4>(ElimDev, double *);
+extern template __global__ void k_elim_basis<8>(ElimDev, double *);
 }
+
+// What daqp_batch_eliminate keeps: the caller's problem (device pointers: borrowed, or the handle's own copies of host arrays), the
+// factor Q, R of the equality rows, x0, c0, the flags and the reduced problem -- everything on one device, launched on one stream.
+struct DAQPBatchElimination {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    daqp_amd::ElimDev d{};
+    std::vector<void *> owned;
+    unsigned long long bytes = 0;
+    double *own_f = nullptr, *own_bu = nullptr, *own_bl = nullptr;      // the handle's copies of host-resident f / bounds
+    int grid = 0;      // workgroup tier: persistent blocks, one n x n scratch matrix each
+};
 
 using namespace daqp_amd;
 
@@ -236,9 +266,260 @@ int certify_run(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_fl
     return st.finish();
 }
 
+// ---- equality elimination (include/daqp_amd.h, eliminate.hip.h)
+template <typename T>
+int elim_alloc(DAQPBatchElimination *el, T **p, size_t count, bool zero = false)
+{
+    if (count == 0) count = 1;
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(p), count * sizeof(T)));
+    el->owned.push_back(*p);
+    el->bytes += count * sizeof(T);
+    if (zero) HIPCHK(hipMemsetAsync(*p, 0, count * sizeof(T), el->stream));
+    return 0;
+}
+// a device copy of a host array in a buffer of the handle's (allocated when first needed)
+template <typename T>
+int elim_copy(DAQPBatchElimination *el, T **own, const T *host, size_t count)
+{
+    if (!*own && elim_alloc(el, own, count)) return DAQP_EXIT_UNSUPPORTED;
+    HIPCHK(hipMemcpyAsync(*own, host, count * sizeof(T), hipMemcpyHostToDevice, el->stream));
+    return 0;
+}
+bool elim_no_device(int *ndev)
+{
+    *ndev = 0;
+    if (hipGetDeviceCount(ndev) != hipSuccess || *ndev == 0) {
+        set_err("no HIP device: libdaqp_amd has no CPU path");
+        return true;
+    }
+    return false;
+}
+template <typename K1, typename K2, typename K4, typename K8>
+auto elim_pick(int n, K1 k1, K2 k2, K4 k4, K8 k8) { const int nv = elim_nv(n); return nv == 1 ? k1 : (nv == 2 ? k2 : (nv == 4 ? k4 : k8)); }
+
+int elim_run(DAQPBatchElimination *el)
+{
+    const ElimDev &d = el->d;
+    // the tier is decided by n alone: one wavefront with H and the reflectors in LDS (69.1 KB at most), a workgroup of four beyond
+    const bool wave = d.n <= 64;
+    const size_t lds = elim_lds_bytes(d.n, d.neq, wave);
+    void (*k)(ElimDev) = elim_pick(d.n, k_eliminate<1, 1>, k_eliminate<2, 4>, k_eliminate<4, 4>, k_eliminate<8, 4>);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3(wave ? d.N : el->grid), dim3(wave ? 64 : 256), lds, el->stream, d);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+// ---- equality elimination: argument checks first, then the device, then the work.  A failed daqp_batch_eliminate leaves no handle.
+int daqp_batch_eliminate(DAQPBatchElimination **out, const DAQPBatchProblem *p, const int *eq_rows, int neq,
+                         const DAQPSettings *settings, int device, void *hip_stream)
+{
+    int ndev = 0;
+    if (out) *out = nullptr;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!out || !p || !eq_rows) { set_err("daqp_batch_eliminate: null out, problem or eq_rows"); return DAQP_EXIT_UNSUPPORTED; }
+    if (p->N <= 0 || p->n <= 0 || p->m < 0 || p->m > (1 << 24) || p->ms < 0 || p->ms > p->n || p->ms > p->m) {
+        set_err("daqp_batch_eliminate: bad dimensions N=%d n=%d m=%d ms=%d (N >= 1, n >= 1, 0 <= m <= 2^24, ms <= n, ms <= m)", p->N, p->n, p->m, p->ms);
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (p->n > 511) { set_err("daqp_batch_eliminate: n = %d: the elimination kernels take n <= 511", p->n); return DAQP_EXIT_UNSUPPORTED; }
+    if (neq < 1 || neq >= p->n) { set_err("daqp_batch_eliminate: neq = %d must be in 1..n-1 (n = %d)", neq, p->n); return DAQP_EXIT_UNSUPPORTED; }
+    for (int c = 0; c < neq; ++c) {
+        if (eq_rows[c] < 0 || eq_rows[c] >= p->m) { set_err("daqp_batch_eliminate: eq_rows[%d] = %d is out of range 0..%d", c, eq_rows[c], p->m - 1); return DAQP_EXIT_UNSUPPORTED; }
+        if (c > 0 && eq_rows[c] <= eq_rows[c - 1]) { set_err("daqp_batch_eliminate: eq_rows must be distinct and ascending (eq_rows[%d] = %d after %d)", c, eq_rows[c], eq_rows[c - 1]); return DAQP_EXIT_UNSUPPORTED; }
+    }
+    if (!p->f || (p->m > p->ms && !p->A) || !p->bupper || !p->blower) { set_err("daqp_batch_eliminate: null f, A or bounds"); return DAQP_EXIT_UNSUPPORTED; }
+    if (p->memory != DAQP_MEM_HOST && p->memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_eliminate: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    if (device >= ndev) { set_err("daqp_batch_eliminate: device %d of %d", device, ndev); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(device));
+    if (device < 64) g_devices_used.fetch_or(1ull << device);
+    DAQPSettings st;
+    if (settings) st = *settings; else daqp_default_settings(&st);
+
+    std::unique_ptr<DAQPBatchElimination, void (*)(DAQPBatchElimination *)> el(new DAQPBatchElimination, daqp_batch_elimination_free);
+    el->device = device;
+    el->stream = reinterpret_cast<hipStream_t>(hip_stream);
+    ElimDev &d = el->d;
+    d.N = p->N; d.n = p->n; d.m = p->m; d.ms = p->ms; d.neq = neq; d.nr = p->n - neq; d.mr = p->m - neq; d.ldn = p->n | 1;
+    d.lp = p->H ? 0 : 1;
+    d.zero_tol = st.zero_tol;
+    const size_t N = d.N, n = d.n, m = d.m, mA = d.m - d.ms, nr = d.nr, mr = d.mr;
+    std::vector<int> kept;
+    for (int r = 0, c = 0; r < d.m; ++r) {
+        if (c < neq && eq_rows[c] == r) ++c;
+        else kept.push_back(r);
+    }
+    int *rows_dev = nullptr, *kept_dev = nullptr;
+    if (elim_alloc(el.get(), &rows_dev, neq) || elim_alloc(el.get(), &kept_dev, mr)) return DAQP_EXIT_UNSUPPORTED;
+    HIPCHK(hipMemcpy(rows_dev, eq_rows, sizeof(int) * neq, hipMemcpyHostToDevice));
+    if (mr) HIPCHK(hipMemcpy(kept_dev, kept.data(), sizeof(int) * mr, hipMemcpyHostToDevice));
+    d.eq_rows = rows_dev; d.kept = kept_dev;
+    if (p->memory == DAQP_MEM_DEVICE) {
+        d.H = p->H; d.f = p->f; d.A = p->A; d.bu = p->bupper; d.bl = p->blower; d.sense = p->sense;
+    } else {
+        double *H = nullptr, *A = nullptr; int *sense = nullptr;
+        if (p->H && elim_copy(el.get(), &H, p->H, N * n * n)) return DAQP_EXIT_UNSUPPORTED;
+        if (mA && elim_copy(el.get(), &A, p->A, N * mA * n)) return DAQP_EXIT_UNSUPPORTED;
+        if (p->sense && elim_copy(el.get(), &sense, p->sense, N * m)) return DAQP_EXIT_UNSUPPORTED;
+        if (elim_copy(el.get(), &el->own_f, p->f, N * n) || elim_copy(el.get(), &el->own_bu, p->bupper, N * m) || elim_copy(el.get(), &el->own_bl, p->blower, N * m))
+            return DAQP_EXIT_UNSUPPORTED;
+        d.H = H; d.A = A; d.sense = sense; d.f = el->own_f; d.bu = el->own_bu; d.bl = el->own_bl;
+    }
+    if (elim_alloc(el.get(), &d.V, N * neq * d.ldn, true) || elim_alloc(el.get(), &d.beta, N * neq) || elim_alloc(el.get(), &d.rd, N * neq) ||
+        elim_alloc(el.get(), &d.rn, N * neq) || elim_alloc(el.get(), &d.x0, N * n) || elim_alloc(el.get(), &d.c0, N) || elim_alloc(el.get(), &d.flags, N) ||
+        elim_alloc(el.get(), &d.Hr, d.lp ? 1 : N * nr * nr) || elim_alloc(el.get(), &d.fr, N * nr) || elim_alloc(el.get(), &d.Ar, N * mr * nr) ||
+        elim_alloc(el.get(), &d.bur, N * mr) || elim_alloc(el.get(), &d.blr, N * mr) || elim_alloc(el.get(), &d.senser, N * mr))
+        return DAQP_EXIT_UNSUPPORTED;
+    if (d.n > 64) {      // persistent workgroups, at most 512 of them and at most 256 MiB of scratch (post-solve's scratch_grid rule)
+        size_t g = ((size_t)256 << 20) / (n * n * sizeof(double));
+        if (g > 512) g = 512;
+        if (g < 16) g = 16;
+        if (g > N) g = N;
+        if (elim_alloc(el.get(), &d.scratch, g * n * n)) return DAQP_EXIT_UNSUPPORTED;
+        el->grid = (int)g;
+    }
+    if (elim_run(el.get())) return DAQP_EXIT_UNSUPPORTED;
+    if (p->memory == DAQP_MEM_HOST) HIPCHK(hipStreamSynchronize(el->stream));      // the host arrays are the caller's again
+    *out = el.release();
+    return 0;
+}
+
+int daqp_batch_eliminate_update(DAQPBatchElimination *el, const c_float *f, const c_float *bupper, const c_float *blower, int memory)
+{
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el) { set_err("daqp_batch_eliminate_update: null handle"); return DAQP_EXIT_UNSUPPORTED; }
+    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_eliminate_update: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(el->device));
+    ElimDev &d = el->d;
+    const size_t N = d.N, n = d.n, m = d.m;
+    if (memory == DAQP_MEM_DEVICE) {
+        if (f) d.f = f;
+        if (bupper) d.bu = bupper;
+        if (blower) d.bl = blower;
+    } else {
+        if (f) { if (elim_copy(el, &el->own_f, f, N * n)) return DAQP_EXIT_UNSUPPORTED; d.f = el->own_f; }
+        if (bupper) { if (elim_copy(el, &el->own_bu, bupper, N * m)) return DAQP_EXIT_UNSUPPORTED; d.bu = el->own_bu; }
+        if (blower) { if (elim_copy(el, &el->own_bl, blower, N * m)) return DAQP_EXIT_UNSUPPORTED; d.bl = el->own_bl; }
+    }
+    void (*k)(ElimDev) = elim_pick(d.n, k_eliminate_update<1>, k_eliminate_update<2>, k_eliminate_update<4>, k_eliminate_update<8>);
+    hipLaunchKernelGGL(k, dim3(d.N), dim3(64), 0, el->stream, d);
+    HIPCHK(hipGetLastError());
+    if (memory == DAQP_MEM_HOST) HIPCHK(hipStreamSynchronize(el->stream));
+    return 0;
+}
+
+int daqp_batch_elimination_problem(DAQPBatchElimination *el, DAQPBatchProblem *reduced)
+{
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el || !reduced) { set_err("daqp_batch_elimination_problem: null handle or problem"); return DAQP_EXIT_UNSUPPORTED; }
+    const ElimDev &d = el->d;
+    reduced->N = d.N; reduced->n = d.nr; reduced->m = d.mr; reduced->ms = 0;
+    reduced->H = d.lp ? nullptr : d.Hr; reduced->f = d.fr; reduced->A = d.Ar; reduced->bupper = d.bur; reduced->blower = d.blr;
+    reduced->sense = d.senser;
+    reduced->memory = DAQP_MEM_DEVICE;
+    return 0;
+}
+
+int daqp_batch_elimination_flags(DAQPBatchElimination *el, int *flags_host)
+{
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el || !flags_host) { set_err("daqp_batch_elimination_flags: null handle or array"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(el->device));
+    HIPCHK(hipMemcpyAsync(flags_host, el->d.flags, sizeof(int) * el->d.N, hipMemcpyDeviceToHost, el->stream));
+    HIPCHK(hipStreamSynchronize(el->stream));
+    return 0;
+}
+
+int daqp_batch_expand(DAQPBatchElimination *el, const DAQPBatchResult *reduced, DAQPBatchResult *full)
+{
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el || !reduced || !full) { set_err("daqp_batch_expand: null handle or result"); return DAQP_EXIT_UNSUPPORTED; }
+    if (!reduced->x || !reduced->lam || !reduced->exitflag) { set_err("daqp_batch_expand: null x, lam or exitflag in the reduced result"); return DAQP_EXIT_UNSUPPORTED; }
+    if ((reduced->memory != DAQP_MEM_HOST && reduced->memory != DAQP_MEM_DEVICE) || (full->memory != DAQP_MEM_HOST && full->memory != DAQP_MEM_DEVICE)) {
+        set_err("daqp_batch_expand: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE");
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (reduced->memory != full->memory) { set_err("daqp_batch_expand: host and device memory mixed in one call (reduced and full results must live on the same side)"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(el->device));
+    const ElimDev &d = el->d;
+    const size_t N = d.N, n = d.n, m = d.m, nr = d.nr, mr = d.mr;
+    ExpandArgs a{};
+    Staging st(nullptr, nullptr, el->stream, full->memory);
+    if (st.in(&a.y, 0, reduced->x, N * nr) || st.in(&a.lamr, 1, reduced->lam, N * mr) || st.in(&a.fvalr, 2, reduced->fval, N) ||
+        st.in(&a.softr, 3, reduced->soft_slack, N) || st.in(&a.flagr, 4, reduced->exitflag, N) || st.in(&a.iterr, 5, reduced->iter, N) ||
+        st.out(&a.x, 6, full->x, N * n) || st.out(&a.lam, 7, full->lam, N * m) || st.out(&a.fval, 8, full->fval, N) ||
+        st.out(&a.soft, 9, full->soft_slack, N) || st.out(&a.exitflag, 10, full->exitflag, N) || st.out(&a.iter, 11, full->iter, N))
+        return DAQP_EXIT_UNSUPPORTED;
+    void (*k)(ElimDev, ExpandArgs) = elim_pick(d.n, k_expand<1>, k_expand<2>, k_expand<4>, k_expand<8>);
+    hipLaunchKernelGGL(k, dim3(d.N), dim3(64), 0, el->stream, d, a);
+    HIPCHK(hipGetLastError());
+    return st.finish();
+}
+
+int daqp_batch_elimination_basis(DAQPBatchElimination *el, c_float *x0, c_float *Z, c_float *c0, int memory)
+{
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el) { set_err("daqp_batch_elimination_basis: null handle"); return DAQP_EXIT_UNSUPPORTED; }
+    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_elimination_basis: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(el->device));
+    const ElimDev &d = el->d;
+    const size_t N = d.N, n = d.n, nr = d.nr;
+    const hipMemcpyKind kind = memory == DAQP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (x0) HIPCHK(hipMemcpyAsync(x0, d.x0, sizeof(double) * N * n, kind, el->stream));
+    if (c0) HIPCHK(hipMemcpyAsync(c0, d.c0, sizeof(double) * N, kind, el->stream));
+    Staging st(nullptr, nullptr, el->stream, memory);
+    double *Zd = nullptr;
+    if (st.out(&Zd, 0, Z, N * n * nr)) return DAQP_EXIT_UNSUPPORTED;
+    if (Zd) {
+        void (*k)(ElimDev, double *) = elim_pick(d.n, k_elim_basis<1>, k_elim_basis<2>, k_elim_basis<4>, k_elim_basis<8>);
+        hipLaunchKernelGGL(k, dim3(d.N), dim3(64), 0, el->stream, d, Zd);
+        HIPCHK(hipGetLastError());
+    }
+    if (memory == DAQP_MEM_HOST) HIPCHK(hipStreamSynchronize(el->stream));
+    return st.finish();
+}
+
+int daqp_batch_elimination_read(DAQPBatchElimination *el, c_float *H, c_float *f, c_float *A, c_float *bupper, c_float *blower, int *sense, int memory)
+{
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el) { set_err("daqp_batch_elimination_read: null handle"); return DAQP_EXIT_UNSUPPORTED; }
+    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("daqp_batch_elimination_read: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE"); return DAQP_EXIT_UNSUPPORTED; }
+    const ElimDev &d = el->d;
+    if (H && d.lp) { set_err("daqp_batch_elimination_read: an LP batch has no reduced H"); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(el->device));
+    const size_t N = d.N, nr = d.nr, mr = d.mr;
+    const hipMemcpyKind kind = memory == DAQP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (H) HIPCHK(hipMemcpyAsync(H, d.Hr, sizeof(double) * N * nr * nr, kind, el->stream));
+    if (f) HIPCHK(hipMemcpyAsync(f, d.fr, sizeof(double) * N * nr, kind, el->stream));
+    if (A && mr) HIPCHK(hipMemcpyAsync(A, d.Ar, sizeof(double) * N * mr * nr, kind, el->stream));
+    if (bupper && mr) HIPCHK(hipMemcpyAsync(bupper, d.bur, sizeof(double) * N * mr, kind, el->stream));
+    if (blower && mr) HIPCHK(hipMemcpyAsync(blower, d.blr, sizeof(double) * N * mr, kind, el->stream));
+    if (sense && mr) HIPCHK(hipMemcpyAsync(sense, d.senser, sizeof(int) * N * mr, kind, el->stream));
+    if (memory == DAQP_MEM_HOST) HIPCHK(hipStreamSynchronize(el->stream));
+    return 0;
+}
+
+unsigned long long daqp_batch_elimination_bytes(const DAQPBatchElimination *el) { return el ? el->bytes : 0; }
+
+void daqp_batch_elimination_free(DAQPBatchElimination *el)
+{
+    if (!el) return;
+    (void)hipSetDevice(el->device);
+    (void)hipStreamSynchronize(el->stream);
+    for (void *p : el->owned) (void)hipFree(p);
+    delete el;
+}
 
 int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory)
 {

@@ -508,6 +508,69 @@ typedef struct {
 } DAQPBatchCertificate;
 int daqp_certify_batch(DAQPBatchCertificate *out, const DAQPBatchProblem *p, const c_float *x, const c_float *lam,
                        int shared /* p->H, p->A are one matrix each */, int device, void *hip_stream);
+/* ---- equality rows of a batch eliminated on the device: reduce, solve the smaller batch, expand (eliminate.hip.h).  An additive front
+ * end: DAQP_UPDATE_eliminate inside daqp_batch_setup / daqp_quadprog stays accepted and ignored.  With C = [first ms rows of I; A]
+ * (m rows), the caller names the equality rows, eq_rows: neq distinct, ascending indices into 0..m-1, 1 <= neq < n, ONE row set for the
+ * whole batch (a simple-bound row fixes a variable).  Per problem, E = C_eq_rows, e = bupper_eq_rows, I = the other m - neq rows
+ * ("kept rows") in their original order:
+ *
+ *        E' = Q [R; 0],  Q = [Q1 Z]     Householder QR, no pivoting, of the rows of E scaled to unit length; Z is n x nr, nr = n - neq
+ *        x0 = Q1 R^-T e                 the minimum-norm solution of E x = e (row scaling undone);   x = x0 + Z y
+ *
+ *   reduced problem, shape (nr, m - neq, ms = 0):
+ *        H_r = Z'HZ  (one triangle, mirrored: exactly symmetric)        f_r = Z'(H x0 + f)        A_r = C_I Z
+ *        bupper_r = bupper_I - C_I x0,  blower_r = blower_I - C_I x0    (a bound with |b| >= DAQP_INF stays as it is)
+ *        sense_r = sense_I              (SOFT, IMMUTABLE, ACTIVE, LOWER carried over: a warm start survives)
+ *                                       A SOFT kept row is weighted in the reduced problem by q_k = c_k Z H_r^-1 Z'c_k', not by c_k H^-1 c_k':
+ *                                       an ACTIVE soft row sits rho_soft q_k lam_k beyond its bound with the reduced q_k, so x, lam and
+ *                                       soft_slack are those of the reduced problem and differ from the unreduced solve by
+ *                                       rho_soft (q_k^full - q_k^reduced) lam_k there.  Inactive soft rows change nothing.
+ *        c0 = 1/2 x0'Hx0 + f'x0         LP batches (H == NULL): H_r == NULL, f_r = Z'f, c0 = f'x0
+ *
+ *   expansion of a reduced result (y, lam_r, fval_r):
+ *        x = x0 + Z y        lam_I = lam_r (back at the original row positions)        fval = fval_r + c0
+ *        lam_E = -R^-1 Q1'(H x + f + C_I'lam_I)   in the caller's units: the full pair satisfies H x + f + C'lam = 0
+ *        exitflag, iter and soft_slack pass through
+ *
+ * Per-problem flags (daqp_batch_elimination_flags): 1; DAQP_EXIT_OVERDETERMINED_INITIAL (-6) when R_jj^2 < settings->zero_tol, the
+ * dependence test of daqp_batch_backward_nullspace -- every reduced array of that problem is zero; DAQP_EXIT_UNSUPPORTED (-8) when
+ * bupper_k != blower_k on a row of eq_rows (no equality problem) -- its x0, f_r, c0 and reduced bounds are zero.  The rest of the batch is
+ * untouched either way, and daqp_batch_expand gives such a problem its flag as exitflag and zero x, lam and fval.
+ *   daqp_batch_eliminate            p: N problems with their own H and A (shared-structure batches are out of scope); eq_rows is host
+ *                                   memory.  Device-resident arrays of p are BORROWED -- H, A, f, the bounds and sense must stay valid
+ *                                   while the handle lives (expansion reads H, f and A); host-resident ones are copied.  One launch on
+ *                                   hip_stream (a hipStream_t; NULL: the null stream) of `device` (-1: the current one).
+ *                                   n <= 64: one wavefront per problem, H and the reflectors in LDS; n <= 511: one workgroup per problem.
+ *                                   ONLY this call has the workgroup tier: update, expand, basis and read run one wavefront per
+ *                                   problem at every n (up to eight entries per lane).
+ *   daqp_batch_eliminate_update     new f and / or bounds (NULL: unchanged) on the kept Q, R: x0, f_r, the reduced bounds, c0 and the
+ *                                   -8 / 1 flags only -- bit for bit what a fresh daqp_batch_eliminate on those data writes.  The warm
+ *                                   path of an MPC loop: follow with daqp_batch_update(DAQP_UPDATE_v | DAQP_UPDATE_d) on the reduced batch.
+ *   daqp_batch_elimination_problem  the reduced problem: device pointers owned by the handle, valid until it is freed
+ *                                   (memory = DAQP_MEM_DEVICE; hand it to daqp_batch_setup of a batch of shape (nr, m - neq, 0))
+ *   daqp_batch_expand               reduced -> full; both results on the same side (host or device); reduced->x, lam and exitflag
+ *                                   are needed, any pointer of `full` may be NULL
+ *   daqp_batch_elimination_basis    x0 (N*n), Z (N*n*nr, row-major n x nr per problem), c0 (N); any may be NULL -- for tests and for
+ *                                   callers who chain derivatives through the elimination themselves
+ *   daqp_batch_elimination_read     copies of the reduced arrays (N*nr*nr, N*nr, N*mr*nr, N*mr, N*mr, N*mr with nr = n - neq,
+ *                                   mr = m - neq); any may be NULL, H must be NULL for an LP batch
+ * Host memory: the call returns when the results are there; device memory: it only enqueues on the handle's stream.
+ * Every entry returns 0, or nonzero with the reason in daqp_amd_last_error() and no device work: neq < 1 or neq >= n; rows out of
+ * range or not ascending; n > 511; a NULL pointer; host and device memory mixed within one call.  Without a HIP device every entry
+ * returns DAQP_EXIT_UNSUPPORTED ("no HIP device").  A failed daqp_batch_eliminate leaves *out NULL.
+ * Not built: DAQP_UPDATE_eliminate in place, per-problem equality sets, shared H / A, the multi-device entry, and backward / refine
+ * through an eliminated batch. */
+typedef struct DAQPBatchElimination DAQPBatchElimination;
+int daqp_batch_eliminate(DAQPBatchElimination **out, const DAQPBatchProblem *p, const int *eq_rows /* host, neq */, int neq,
+                         const DAQPSettings *settings, int device, void *hip_stream);
+int daqp_batch_eliminate_update(DAQPBatchElimination *el, const c_float *f, const c_float *bupper, const c_float *blower, int memory); /* NULL: unchanged */
+int daqp_batch_elimination_problem(DAQPBatchElimination *el, DAQPBatchProblem *reduced);  /* device pointers owned by el; valid until free */
+int daqp_batch_elimination_flags(DAQPBatchElimination *el, int *flags_host);              /* 1, -6, -8 per problem */
+int daqp_batch_expand(DAQPBatchElimination *el, const DAQPBatchResult *reduced, DAQPBatchResult *full);
+int daqp_batch_elimination_basis(DAQPBatchElimination *el, c_float *x0 /* N*n */, c_float *Z /* N*n*nr */, c_float *c0 /* N */, int memory);
+int daqp_batch_elimination_read(DAQPBatchElimination *el, c_float *H, c_float *f, c_float *A, c_float *bupper, c_float *blower, int *sense, int memory);
+unsigned long long daqp_batch_elimination_bytes(const DAQPBatchElimination *el);
+void daqp_batch_elimination_free(DAQPBatchElimination *el);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 
