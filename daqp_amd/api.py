@@ -316,7 +316,7 @@ class BatchModel:
 
     _BW_KEYS = ("dz", "dbupper", "dblower", "qsoft", "usoft", "usoft_id")
 
-    def backward(self, grad_x, out="torch", nullspace=False):
+    def backward(self, grad_x, out="torch", nullspace=False, grad_lam=None):
         """The adjoint of the last solve (daqp_batch_backward, include/daqp_amd.h): for grad_x = dl/dx of shape (N, n) returns
         dict(dz, dbupper, dblower, status) with dl/df = -dz, dl/dH = -1/2 (dz x' + x dz'), dl/dA_i = -(lam_i dz + dnu_i x)' on the
         general rows of the working set (dnu = dbupper + dblower), dl/dbupper = dbupper, dl/dblower = dblower.  status (N,) int32:
@@ -330,10 +330,17 @@ class BatchModel:
         nullspace=True: daqp_batch_backward_nullspace with which = 0 -- problems that went through the proximal loop (singular H,
         LPs; status -8 otherwise) get their adjoint from the null-space kernel on the caller's own H, every other problem comes
         out bit for bit as without it.  nullspace="all": which = 1, every problem through that kernel.  n <= 64 ("all" is refused
-        beyond, True leaves the -8), ns_max == 0, and H / A given as device tensors must still be alive and unchanged."""
+        beyond, True leaves the -8), ns_max == 0, and H / A given as device tensors must still be alive and unchanged.
+
+        grad_lam (N, m) = dl/dlam with respect to the signed multipliers of the solve: daqp_batch_backward_dual -- the same system
+        with grad_lam on the working set in the second block of its right-hand side, the same outputs and the same formulas.
+        grad_x may then be None (= 0).  nullspace selects its `which` (False: -1, True: 0, "all": 1); ns_max == 0 only.  Without
+        grad_lam the calls above are made, unchanged."""
         N, n, m, ns = self.N, self.n, self.m, self.ns
         if nullspace not in (False, True, "all"):
             raise ValueError('nullspace must be False, True or "all"')
+        if grad_lam is not None:
+            return self._backward_dual(grad_x, grad_lam, out, -1 if nullspace is False else (1 if nullspace == "all" else 0))
         keep = []
         if out == "torch":
             dev = torch.device("cuda", self.device)
@@ -367,6 +374,31 @@ class BatchModel:
         if rc != 0:
             raise RuntimeError(f"{entry} failed ({rc}): {_lib.last_error()}")
         self._bw_keep = [keep, o]      # the launch reads / writes them after this call has returned
+        return o
+
+    def _backward_dual(self, grad_x, grad_lam, out, which):
+        N, n, m = self.N, self.n, self.m
+        if out == "torch":
+            dev = torch.device("cuda", self.device)
+            conv = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+            ptr = lambda a: None if a is None else a.data_ptr()
+            f64, i32, mem = torch.float64, torch.int32, MEM_DEVICE
+        else:
+            conv = lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64)
+            new = lambda shape, dtype: np.empty(shape, dtype)
+            ptr = lambda a: None if a is None else a.ctypes.data
+            f64, i32, mem = np.float64, np.int32, MEM_HOST
+        g, gl = conv(grad_x), conv(grad_lam)
+        if g is not None and tuple(g.shape) != (N, n):
+            raise ValueError(f"grad_x must have shape {(N, n)}")
+        if tuple(gl.shape) != (N, m):
+            raise ValueError(f"grad_lam must have shape {(N, m)}")
+        o = dict(dz=new((N, n), f64), dbupper=new((N, m), f64), dblower=new((N, m), f64), status=new((N,), i32))
+        rc = lib().daqp_batch_backward_dual(self._h, ptr(g), ptr(gl), ptr(o["dz"]), ptr(o["dbupper"]), ptr(o["dblower"]), ptr(o["status"]), which, mem)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_backward_dual failed ({rc}): {_lib.last_error()}")
+        self._bw_keep = [[g, gl], o]      # the launch reads / writes them after this call has returned
         return o
 
     def certify(self, res, out=None):

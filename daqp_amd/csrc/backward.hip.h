@@ -29,6 +29,13 @@
 // scaling[i] (true row = stored row / scaling[i]) unless H was diagonal (QState::diag_h: rows kept as they are).  The division is
 // folded into the vectors that meet those rows (g, the rows of A, the result), so every output is in the caller's unscaled units.
 //
+// A dual right-hand side (DUAL == true: daqp_batch_backward_dual).  A loss that also depends on the signed multipliers lam_W puts
+// g_lamW[k] = grad_lam[WS[k]] into the second block, K [dz; dnu] = [g; g_lamW], and only the Gram system's right-hand side changes:
+//     (N_W N_W') dnu = N_W w - g_lamW
+// The rows of N_W are rebuilt unscaled (the scaling[] of the rows < ms of R^-1 is folded into them), so g_lamW is already in their
+// units and meets the unit-length scaling alone: rhs_k = (N_k w - g_lamW_k) / |N_k|.  grad_x may be null (= 0) there.  With W empty
+// grad_lam is not read.  DUAL == false compiles to what the kernel was before.
+//
 // Mapping: one workgroup per problem; T = 64 (ONE wavefront, R^-1, the rows and the Gram matrix in LDS) while n <= 64 and all of it
 // fits (with ns_max = 0 the working set holds at most 65 rows and it always does) -- and T = 256 beyond, R^-1 streamed from HBM, rows and Gram matrix in LDS where they fit (NL) and
 // in a per-WORKGROUP scratch in HBM where they do not (persistent workgroups, problem q, q + grid, ...).  All arithmetic is fp64.
@@ -45,6 +52,7 @@ struct BackwardArgs {
     size_t scratch_per_wg;
     double *qsoft, *usoft;        // [N][m], [N][ns_max][n]: SOFT kernels only, each may be null
     int *usoft_id;                // [N][ns_max], may be null
+    const double *grad_lam;       // [N][m]: DUAL kernels only (read on W); grad_x may be null there (= 0)
 };
 
 // LDS of one workgroup in bytes: w, g', rs (n each), rhs, y, sn, dg (cap each), then R^-1 (RL), rows + Gram (NL), ids, side, flag
@@ -57,7 +65,7 @@ __host__ __device__ inline size_t backward_lds_bytes(int n, int cap, bool rl, bo
 }
 __host__ __device__ inline size_t backward_scratch_doubles(int n, int cap) { return (size_t)cap * (n | 1) + (size_t)tri(cap); }
 
-template <int T, bool RL, bool NL, bool SOFT>
+template <int T, bool RL, bool NL, bool SOFT, bool DUAL = false>
 __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
 {
     extern __shared__ double lds_bw[];
@@ -99,12 +107,13 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
             const double *R = Rg;
             if constexpr (RL) { for (int e = tid; e < b.rtri; e += T) Rl[e] = Rg[e]; R = Rl; }
             const int diag = qs->diag_h;
-            const double *g = a.grad_x + (size_t)q * n;
+            const double *g = (DUAL && !a.grad_x) ? nullptr : a.grad_x + (size_t)q * n;
             if (tid == 0) *bad = 0;
             for (int i = tid; i < n; i += T) {
                 const double s = (i < ms && !diag) ? 1.0 / sc[i] : 1.0;
                 rs[i] = s;
-                gp[i] = g[i] * s;
+                if constexpr (DUAL) gp[i] = g ? g[i] * s : 0.0;
+                else gp[i] = g[i] * s;
             }
             __syncthreads();
             for (int k = tid; k < na; k += T) {
@@ -173,7 +182,12 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
                         if (l <= k) G[tri(k) + l] *= sn[k] * sn[l];
                     }
                 }
-                for (int k = tid; k < na; k += T) rhs[k] *= sn[k];
+                if constexpr (DUAL) {      // N_W w - g_lamW: the rows above are unscaled already, so sn is all that meets g_lam
+                    const double *gl = a.grad_lam + (size_t)q * m;
+                    for (int k = tid; k < na; k += T) rhs[k] = (rhs[k] - gl[ids[k]]) * sn[k];
+                } else {
+                    for (int k = tid; k < na; k += T) rhs[k] *= sn[k];
+                }
                 // ---- Cholesky in place (right-looking), diagonal in dg; a pivot below zero_tol ends it
                 for (int c = 0; c < na; ++c) {
                     __syncthreads();

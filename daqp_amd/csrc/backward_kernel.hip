@@ -11,6 +11,11 @@ template __global__ void k_backward<256, false, false, false>(BatchDev, Backward
 template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
 template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
 template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
+// a dual right-hand side (daqp_batch_backward_dual): g_lam on W in the second block
+template __global__ void k_backward<64, true, true, false, true>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, true, false, true>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, false, false, true>(BatchDev, BackwardArgs);
 // the null-space adjoint: the caller's H instead of the kept factor (singular H, LPs)
 template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
+template __global__ void k_backward_nullspace<64, true>(BatchDev, NullspaceArgs);
 }

@@ -21,6 +21,12 @@
 //     4. solve     dz = Z Hr^-1 Z'g,   R dnu~ = Q1'(g - H dz),   dnu = dnu~ / |row|,   scattered to dbupper / dblower by the row's
 //                  DAQP_LOWER bit exactly as k_backward does
 //
+// A dual right-hand side (DUAL == true: daqp_batch_backward_dual): K [dz; dnu] = [g; g_lamW], g_lamW[c] = grad_lam[WS[c]] the gradient
+// with respect to the signed multipliers.  Steps 1 - 3 and both singularity tests are unchanged; step 4 becomes the step algebra of
+// refine_nullspace.hip.h with r1 = g, r2 = g_lamW (s = the norms of the rows):
+//     y = R^-T (g_lamW / s),   z = Hr^-1 (Q'(g - H Q [y; 0]))[k:],   dz = Q [y; z],   dnu = R^-1 (Q'(g - H dz))[:k] / s
+// At an LP vertex (k = n) dz = Q y is no longer zero.  grad_x may be null (= 0).  DUAL == false compiles to what the kernel was.
+//
 // The system does not contain x or lam: the result depends on H, A and W only, not on how tightly the proximal loop converged.
 //
 // What is read: WS, QState, sense, A as k_backward reads them, and the caller's H through BatchDev::H (indexed with qf() for shared
@@ -43,6 +49,7 @@ struct NullspaceArgs {
     int *status;                    // [N]
     int lp;                         // the batch is an LP batch: b.H is the setup's identity, H = 0
     int only_prox;                  // 1: only the problems with n_prox > 0 (the others were written by k_backward and stay untouched)
+    const double *grad_lam;         // [N][m]: DUAL kernel only (read on W); grad_x may be null there (= 0)
 };
 
 __host__ __device__ inline size_t nullspace_lds_bytes(int n) { return ((size_t)n * (n | 1) + 3 * (size_t)n) * sizeof(double); }
@@ -80,7 +87,7 @@ __device__ __forceinline__ double ns_hmul(const double *H, double x, int lane, i
 }
 
 // (a template only so that backward_kernel.hip holds the one instantiation: T is the wavefront, 64)
-template <int T>
+template <int T, bool DUAL = false>
 __global__ __launch_bounds__(T) void k_backward_nullspace(BatchDev b, NullspaceArgs a)
 {
     static_assert(T == 64, "one wavefront per problem");
@@ -109,7 +116,7 @@ __global__ __launch_bounds__(T) void k_backward_nullspace(BatchDev b, NullspaceA
     const double *Aq = b.A + (b.shared ? qF : (size_t)q) * mA * n;
     const int nz = n - k, ldz = nz | 1;
     double *Hr = V + (size_t)k * ldn;      // element (r, c), r >= c, at Hr[c * ldz + r]
-    const double g = (st == 0 && lane < n) ? a.grad_x[(size_t)q * n + lane] : 0.0;
+    const double g = (st == 0 && lane < n && !(DUAL && !a.grad_x)) ? a.grad_x[(size_t)q * n + lane] : 0.0;
 
     // ---- 1, 2: the rows of C_W, unit length, and the QR of C_W' one column at a time
     for (int c = 0; st == 0 && c < k; ++c) {
@@ -165,7 +172,41 @@ __global__ __launch_bounds__(T) void k_backward_nullspace(BatchDev b, NullspaceA
 
     // ---- 4: dz = Z Hr^-1 Z'g, then R dnu~ = Q1'(g - H dz)
     double dz = 0.0;
-    if (st == 0 && nz > 0) {
+    if constexpr (DUAL) {
+        if (st == 0) {
+            // y = R^-T (g_lamW / s), lane i owns entry i (R sits above the reflectors: R(c, i) at V[i * ldn + c])
+            double w = 0.0;
+            if (lane < k) w = a.grad_lam[(size_t)q * m + b.WS[(size_t)q * cap + lane]] / rn[lane];
+            for (int c = 0; c < k; ++c) {
+                const double yc = __shfl(w, c, 64) / rd[c];
+                if (lane == c) w = yc;
+                else if (lane > c && lane < k) w -= V[(size_t)lane * ldn + c] * yc;
+            }
+            if (nz > 0) {
+                // t = g - H Q [y; 0], then z = Hr^-1 (Q't)[k:]
+                double p = w;
+                for (int c = k - 1; c >= 0; --c) p = ns_reflect(p, V, beta, c, ldn, lane, n);
+                double t = g - ns_hmul(H, p, lane, n, 0);
+                for (int c = 0; c < k; ++c) t = ns_reflect(t, V, beta, c, ldn, lane, n);
+                double rhs = __shfl(t, (lane + k) & 63, 64);      // lane r < nz takes entry k + r
+                if (lane >= nz) rhs = 0.0;
+                for (int c = 0; c < nz; ++c) {      // L y1 = rhs
+                    const double yc = __shfl(rhs, c, 64) / Hr[(size_t)c * ldz + c];
+                    if (lane == c) rhs = yc;
+                    else if (lane > c && lane < nz) rhs -= Hr[(size_t)c * ldz + lane] * yc;
+                }
+                for (int c = nz - 1; c >= 0; --c) {      // L' y2 = y1
+                    const double yc = __shfl(rhs, c, 64) / Hr[(size_t)c * ldz + c];
+                    if (lane == c) rhs = yc;
+                    else if (lane < c) rhs -= Hr[(size_t)lane * ldz + c] * yc;
+                }
+                const double z = __shfl(rhs, (lane - k) & 63, 64);      // back to entry k + r of an n-vector
+                if (lane >= k && lane < n) w = z;
+            }
+            dz = w;      // dz = Q [y; z]
+            for (int c = k - 1; c >= 0; --c) dz = ns_reflect(dz, V, beta, c, ldn, lane, n);
+        }
+    } else if (st == 0 && nz > 0) {
         double y = g;
         for (int c = 0; c < k; ++c) y = ns_reflect(y, V, beta, c, ldn, lane, n);
         // lane r < nz takes entry k + r of Q'g

@@ -19,7 +19,11 @@ extern template __global__ void k_backward<256, false, false, false>(BatchDev, B
 extern template __global__ void k_backward<64, true, true, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, true, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<64, true, true, false, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, true, false, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, false, false, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
+extern template __global__ void k_backward_nullspace<64, true>(BatchDev, NullspaceArgs);
 // the elimination kernels: eliminate_kernel.hip
 extern template __global__ void k_eliminate<1, 1>(ElimDev);
 extern template __global__ void k_eliminate<2, 4>(ElimDev);
@@ -131,8 +135,10 @@ struct Staging {
 // nsw: the null-space kernel (nullspace.hip.h) on the same stream -- -1: not at all; 0: behind k_backward, for the problems that went
 // through the proximal loop only (it overwrites their outputs; every other problem keeps k_backward's bits); 1: instead of k_backward,
 // for every problem.  Launched for n <= 64 only: beyond, nsw == 0 leaves k_backward's DAQP_EXIT_UNSUPPORTED and nsw == 1 was refused.
+// grad_lam != null (daqp_batch_backward_dual, ns_max == 0 only): the DUAL instantiations of both kernels -- g_lam on W in the second
+// block of the right-hand side -- with the same tiers (they need no LDS of their own: backward_lds_bytes is unchanged); grad_x may then be null.
 int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
-                    c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory, int nsw = -1)
+                    c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory, int nsw = -1, const c_float *grad_lam = nullptr)
 {
     if (!b->is_setup || !b->solved || b->pending_mask) {
         set_err("%s: the last operation on the batch was not a successful daqp_batch_solve", who);
@@ -147,6 +153,7 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
     if (!t.fits && nsw != 1) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
     void (*kb)(BatchDev, BackwardArgs);
     if (soft) kb = t.small ? k_backward<64, true, true, true> : (t.nl ? k_backward<256, false, true, true> : k_backward<256, false, false, true>);
+    else if (grad_lam) kb = t.small ? k_backward<64, true, true, false, true> : (t.nl ? k_backward<256, false, true, false, true> : k_backward<256, false, false, false, true>);
     else kb = t.small ? k_backward<64, true, true, false> : (t.nl ? k_backward<256, false, true, false> : k_backward<256, false, false, false>);
     BackwardArgs a{};
     int grid = d.N;
@@ -158,7 +165,7 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
     Staging st(b, b->adjoint.slot, b->stream, memory);
     if (st.in(&a.grad_x, 0, grad_x, N * n) || st.out(&a.dz, 1, dz, N * n) || st.out(&a.dbupper, 2, dbupper, N * m) ||
         st.out(&a.dblower, 3, dblower, N * m) || st.out(&a.qsoft, 4, qsoft, N * m) || st.out(&a.usoft, 5, usoft, N * ns * n) ||
-        st.out(&a.usoft_id, 6, usoft_id, N * ns) || st.out(&a.status, 7, status, N))
+        st.out(&a.usoft_id, 6, usoft_id, N * ns) || st.out(&a.status, 7, status, N) || st.in(&a.grad_lam, 8, grad_lam, N * m))
         return DAQP_EXIT_UNSUPPORTED;
     if (nsw != 1) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
@@ -170,9 +177,11 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
         na.grad_x = a.grad_x; na.dz = a.dz; na.dbupper = a.dbupper; na.dblower = a.dblower; na.status = a.status;
         na.lp = (b->ident && d.H == b->ident) ? 1 : 0;
         na.only_prox = nsw == 0 ? 1 : 0;
+        na.grad_lam = a.grad_lam;
+        void (*kn)(BatchDev, NullspaceArgs) = grad_lam ? k_backward_nullspace<64, true> : k_backward_nullspace<64>;
         const size_t lds_ns = nullspace_lds_bytes(d.n);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_backward_nullspace<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ns));
-        hipLaunchKernelGGL(k_backward_nullspace<64>, dim3(d.N), dim3(64), lds_ns, b->stream, d, na);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ns));
+        hipLaunchKernelGGL(kn, dim3(d.N), dim3(64), lds_ns, b->stream, d, na);
         HIPCHK(hipGetLastError());
     }
     return st.finish();
@@ -553,6 +562,22 @@ int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c
         else memset(qsoft, 0, bytes);
     }
     return rc;
+}
+
+// The adjoint with a dual right-hand side (include/daqp_amd.h): K [dz; dnu] = [grad_x; grad_lam on W].  grad_lam == NULL is the
+// existing entry for the same `which`, kernels and all; otherwise the DUAL instantiations run in the same places.
+int daqp_batch_backward_dual(DAQPBatch *b, const c_float *grad_x, const c_float *grad_lam, c_float *dz, c_float *dbupper, c_float *dblower,
+                             int *status, int which, int memory)
+{
+    if (!b || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_dual: null batch or output array"); return DAQP_EXIT_UNSUPPORTED; }
+    if (!grad_x && !grad_lam) { set_err("daqp_batch_backward_dual: grad_x and grad_lam are both null: there is nothing to differentiate"); return DAQP_EXIT_UNSUPPORTED; }
+    if (which < -1 || which > 1) { set_err("daqp_batch_backward_dual: which must be -1 (Gram only), 0 (null space for the proximal problems) or 1 (null space for every problem)"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->ns_max > 0) { set_err("daqp_batch_backward_dual: batches created with ns_max > 0 (soft constraints) are not supported: the multiplier of a soft row is not built here"); return DAQP_EXIT_UNSUPPORTED; }
+    if (which == 1 && b->d.n > 64) { set_err("daqp_batch_backward_dual: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", b->d.n); return DAQP_EXIT_UNSUPPORTED; }
+    if (which >= 0 && b->is_setup && b->d.H == nullptr) { set_err("daqp_batch_backward_dual: the batch has no Hessian of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
+    if (!grad_lam) return which < 0 ? daqp_batch_backward(b, grad_x, dz, dbupper, dblower, status, memory)
+                                    : daqp_batch_backward_nullspace(b, grad_x, dz, dbupper, dblower, status, which, memory);
+    return backward_launch("daqp_batch_backward_dual", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory, which, grad_lam);
 }
 
 // Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h): refine_launch above

@@ -20,8 +20,15 @@ the caller's own H: QR of the active rows, Cholesky of Z'HZ -- and the same form
 a problem is differentiable where its optimum is locally unique: independent active rows (R_jj^2 >= zero_tol) and Z'HZ positive
 definite (pivots > zero_tol max(1, max_i H_ii)); an LP must sit at a vertex.  n <= 64, no SOFT rows.
 
-Out of scope: gradients of lam, fval or soft_slack, per-row soft weights, proximal problems with n > 64 or with SOFT rows, an LP
-with one shared A.
+qp_layer(..., returns=("x", "lam", "fval")) also hands back the signed multipliers lam (N, m) and the optimal value fval (N,) as
+differentiable tensors.  Backward is still ONE launch -- daqp_batch_backward_dual: the same system with g_lam on the working set in
+the second block of its right-hand side -- and the formulas above, unchanged.  A gradient g_fval through fval = 1/2 x'Hx + f'x needs
+no solve (envelope theorem) and is added in torch:
+
+    dl/df += g_fval x      dl/dH += 1/2 g_fval x x'      dl/dbupper_i, dl/dblower_i += -g_fval lam_i (the row's side)      dl/dA_i += g_fval lam_i x'
+
+Out of scope: gradients of soft_slack, lam or fval of batches with SOFT rows, per-row soft weights, proximal problems with n > 64 or
+with SOFT rows, an LP with one shared A.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -60,7 +67,7 @@ def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms):
 
 class _QPLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft, nullspace=False):
+    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft, nullspace=False, returns=None):
         if not f.is_cuda:
             raise ValueError("qp_layer needs its inputs on the GPU")
         N, n = f.shape
@@ -103,15 +110,22 @@ class _QPLayer(torch.autograd.Function):
         ctx.rho_like = rho_soft if isinstance(rho_soft, torch.Tensor) else None
         ctx.ms, ctx.shared, ctx.strict, ctx.info = ms, shared, strict, info
         ctx.nullspace = bool(nullspace)
+        ctx.returns, ctx.exitflag = returns, r["exitflag"]
         if info is not None:
             info["exitflag"] = r["exitflag"]
             info["lam"] = r["lam"]
+        if returns is not None:      # a tuple of names: x, lam, fval in the caller's order; a gradient nobody sent stays None
+            ctx.set_materialize_grads(False)
+            return tuple(r[k].clone() for k in returns)
         return r["x"].clone()      # (the kept copy is what backward multiplies with, whatever the caller does to its own)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, grad_x):
+    def backward(ctx, *grads):
         bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
+        if ctx.returns is not None:
+            return _QPLayer._backward_returns(ctx, dict(zip(ctx.returns, grads)))
+        grad_x, = grads
         with torch.cuda.device(x.device):
             o = bm.backward(grad_x.to(torch.float64).contiguous(), out="torch", nullspace=ctx.nullspace)
         status = o["status"]
@@ -155,8 +169,71 @@ class _QPLayer(torch.autograd.Function):
             grho = grho.to(device=like.device, dtype=like.dtype).reshape(like.shape)
         return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho, None
 
+    @staticmethod
+    def _backward_returns(ctx, g):
+        """backward of returns=(...): one adjoint launch with g_x and g_lam (none when only fval carries a gradient), the formulas of
+        the module docstring, then the envelope terms of g_fval"""
+        bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
+        c = lambda t: None if t is None else t.to(torch.float64).contiguous()
+        gx, gl, gv = c(g.get("x")), c(g.get("lam")), c(g.get("fval"))
+        none = (None,) * 13
+        if gx is None and gl is None and gv is None:
+            return none
+        o = None
+        with torch.cuda.device(x.device):
+            if gl is not None:
+                o = bm.backward(gx, out="torch", nullspace=ctx.nullspace, grad_lam=gl)
+            elif gx is not None:
+                o = bm.backward(gx, out="torch", nullspace=ctx.nullspace)
+        # (no launch: the envelope terms exist wherever the solve ended optimal)
+        status = o["status"] if o is not None else torch.where(ctx.exitflag == 1, torch.zeros_like(ctx.exitflag), ctx.exitflag)
+        if ctx.info is not None:
+            ctx.info["status"] = status
+        if ctx.strict:
+            badq = torch.nonzero(status).flatten()
+            if badq.numel():
+                q = int(badq[0])
+                raise RuntimeError(f"qp_layer: {badq.numel()} of {bm.N} problems have no derivative (first: problem {q}, status "
+                                   f"{int(status[q])}); strict=False gives them zero gradients")
+        need = ctx.needs_input_grad
+        gH = gf = gA = gbu = gbl = None
+        add = lambda a, b: b if a is None else a + b
+        if o is not None:
+            dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
+            if need[0]:
+                gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
+            if need[1]:
+                gf = -dz
+            if need[2]:
+                lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
+                gA = -(lg.t() @ dz + ng.t() @ x) if ctx.shared else -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
+            if need[3]:
+                gbu = dbu
+            if need[4]:
+                gbl = dbl
+        if gv is not None:
+            gv = gv * (status == 0)      # a problem without a derivative gets zero gradients here as well
+            if need[0]:
+                gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
+            if need[1]:
+                gf = add(gf, gv[:, None] * x)
+            if need[2]:
+                lg = gv[:, None] * lam[:, ms:]
+                gA = add(gA, lg.t() @ x if ctx.shared else lg[:, :, None] * x[:, None, :])
+            if need[3]:
+                gbu = add(gbu, -gv[:, None] * lam.clamp(min=0.0))      # lam_i > 0: the row sits at its upper bound
+            if need[4]:
+                gbl = add(gbl, -gv[:, None] * lam.clamp(max=0.0))
+        if need[0] and ctx.shared and gH is not None and gH.dim() == 3:
+            gH = gH.sum(0)
+        return gH, gf, gA, gbu, gbl, None, None, None, None, None, None, None, None
 
-def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, nullspace=False, **settings):
+
+RETURNS = ("x", "lam", "fval")
+
+
+def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, nullspace=False, returns="x",
+             **settings):
     """x* (N, n) of  min 1/2 x'Hx + f'x  s.t.  blower <= [x[:ms]; A x] <= bupper  for N problems, differentiable.
 
     H (N, n, n), f (N, n), A (N, mA, n) or None, bupper / blower (N, m) with m = ms + mA (ms defaults to m - mA; blower None =
@@ -175,7 +252,23 @@ def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sens
     nullspace=True: backward is daqp_batch_backward_nullspace -- problems that went through the proximal loop are differentiated
     too (null-space method on H itself; n <= 64, no SOFT rows), every other problem as without it.  H may then be a positive
     semi-definite matrix, or None: an LP batch with per-problem A (N, mA, n) -- dl/dH is None, dl/df, dl/dA, dl/dbupper and
-    dl/dblower come from the same formulas with the x and lam of the solve.  An LP is differentiable at a vertex only."""
-    if nullspace and sense is not None and bool(((torch.as_tensor(sense) & SOFT) != 0).any()):
+    dl/dblower come from the same formulas with the x and lam of the solve.  An LP is differentiable at a vertex only.
+
+    returns: "x" (the default: x* alone), or one or several of "x", "lam", "fval" in any order -- ("x", "lam", "fval"), "fval", ... --
+    for a tuple of differentiable tensors in that order (a single name other than "x" gives that one tensor): x (N, n), the signed
+    multipliers lam (N, m) (> 0 at an upper bound, < 0 at a lower one, 0 off the working set) and fval (N,) = 1/2 x'Hx + f'x.
+    Backward is one daqp_batch_backward_dual launch for the gradients through x and lam; the gradient through fval is added in
+    torch without a solve.  With a gradient through fval alone nothing is launched and status is 0 wherever the solve ended
+    optimal.  Not with SOFT rows."""
+    has_soft = sense is not None and bool(((torch.as_tensor(sense) & SOFT) != 0).any())
+    if nullspace and has_soft:
         raise ValueError("qp_layer: nullspace=True does not take SOFT rows")
-    return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, nullspace)
+    if isinstance(returns, str) and returns == "x":
+        return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, nullspace)
+    names = (returns,) if isinstance(returns, str) else tuple(returns)
+    if not names or len(set(names)) != len(names) or any(k not in RETURNS for k in names):
+        raise ValueError(f'qp_layer: returns must be "x" or distinct names out of {RETURNS} (got {returns!r})')
+    if has_soft:
+        raise ValueError('qp_layer: returns other than "x" does not take SOFT rows: their multipliers and objective are not differentiated')
+    out = _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, nullspace, names)
+    return out[0] if isinstance(returns, str) else out

@@ -332,7 +332,7 @@ int daqp_batch_reset(DAQPBatch *b);
  *   - the batch was created with ns_max > 0: SOFT CONSTRAINTS ARE OUT OF SCOPE of this entry point (they change the (2,2) block
  *     of the system and need more outputs): daqp_batch_backward_soft below takes such batches,
  *   - a pointer is NULL.
- * Not differentiated: lam, fval. */
+ * Gradients through lam and fval: daqp_batch_backward_dual below. */
 int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory);
 /* Fixed-precision iterative refinement of (x, lam) at the working set of the last daqp_batch_solve.  The solve works in the
  * least-distance coordinates and transforms back through the computed R^-1, so its optimum carries an error of about
@@ -467,6 +467,41 @@ int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c
  *   - batches created with ns_max > 0 are refused: q_k = c_k H^-1 c_k' of a soft row does not exist for a singular H. */
 int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status,
                                   int which, int memory);
+/* The adjoint with a DUAL right-hand side: a loss l(x, lam, fval) that also depends on the signed multipliers the solve returned
+ * (lam_k > 0 at an upper bound, < 0 at a lower one; the rows C_W are unsigned, as everywhere here).  With g_x = dl/dx (grad_x: N*n)
+ * and g_lamW[k] = grad_lam[WS[k]] (grad_lam: N*m, dl/dlam in the caller's units) the call solves, at the stored working set W,
+ *
+ *        [ H    C_W' ] [ dz  ]   [ g_x    ]
+ *        [ C_W  0    ] [ dnu ] = [ g_lamW ]
+ *
+ * -- the system of daqp_batch_backward with a second block in its right-hand side; on the kept factor H = R'R only the Gram system
+ * changes, (N_W N_W') dnu = N_W w - g_lamW, and on the null-space route the solve becomes y = R^-T (g_lamW / s),
+ * z = Hr^-1 (Q'(g_x - H Q [y; 0]))[k:], dz = Q [y; z], dnu = R^-1 (Q'(g_x - H dz))[:k] / s (at an LP vertex, k = n, dz is no longer zero).
+ * THE FIVE GRADIENT FORMULAS ARE UNCHANGED:  dl/df = -dz,  dl/dH = -1/2 (dz x' + x dz'),  dl/dA_i = -(lam_i dz + dnu_i x)' for the general
+ * rows i in W,  dl/dbupper = dbupper,  dl/dblower = dblower  (dnu_i on the side where the row sits).  grad_lam is read on W only: the
+ * multiplier of a row off W is identically 0 near the optimum and has no derivative.  A problem with W empty (the unconstrained
+ * shortcut) ignores grad_lam.
+ * A gradient g_fval = dl/dfval through  fval = 1/2 x'Hx + f'x  needs no solve (envelope theorem); the caller adds
+ *
+ *        dl/df += g_fval x        dl/dH += 1/2 g_fval x x'
+ *        dl/dbupper_i, dl/dblower_i += -g_fval lam_i   (on the side where row i of W sits)
+ *        dl/dA_i += g_fval lam_i x'                    (general rows i in W)
+ *
+ *   which == -1   the Gram route only: outputs, status rules, stream, memory semantics and preconditions of daqp_batch_backward
+ *   which == 0/1  as daqp_batch_backward_nullspace: 0 -- the Gram kernel first, then the null-space kernel for the problems with
+ *                 n_prox > 0; 1 -- the null-space kernel for every problem.  Status rules, singularity tests and the validity of the
+ *                 adopted H and A are those of that entry.
+ * grad_x may be NULL (= 0), grad_lam may be NULL (= 0), not both.  With grad_lam == NULL the outputs are bit for bit those of the
+ * existing entry for the same `which`; with grad_lam all zeros they compare equal to them.  `memory` applies to all six arrays.
+ * Returns nonzero, with the reason in the last-error string and without any device work, when both gradients are NULL, an output is
+ * NULL, which is outside -1..1, which == 1 with n > 64, the last operation on the batch was not a successful daqp_batch_solve, or the
+ * batch was created with ns_max > 0.
+ * Not built: soft rows (ns_max > 0 is refused), soft_slack gradients, Jacobians and multi-RHS solves, n > 64 on the null-space
+ * route, EliminatedBatchModel, MultiBatchModel. */
+int daqp_batch_backward_dual(DAQPBatch *b, const c_float *grad_x /* N*n, may be NULL = 0 */,
+                             const c_float *grad_lam /* N*m, may be NULL = 0 */,
+                             c_float *dz, c_float *dbupper, c_float *dblower, int *status,
+                             int which /* -1: Gram only; 0 / 1: as daqp_batch_backward_nullspace */, int memory);
 /* ---- the certificate of a batch of (x, lam) pairs: KKT residuals and Farkas measures, on the device, in twice the working precision
  * (certify.hip.h).  Stateless: no DAQPBatch, no exit flags -- it reads the caller's H, f, A, bupper, blower, sense, x and lam and nothing
  * else, so it certifies the answer of any solver and depends on no adopted pointer.  With C = [I_ms ; A] and the reference's sign

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time of BatchModel.backward next to the forward step it follows, at the two headline shapes of BASELINE.md.
 
-  python tools/bench_backward.py [--configs C2,C3] [--soft | --nullspace] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
+  python tools/bench_backward.py [--configs C2,C3] [--soft | --nullspace | --dual] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
 
 Per shape: N device-resident QPs (daqp_amd.synthetic.generate_batch_torch), forward = BatchModel.setup + solve with device outputs,
 backward = one BatchModel.backward on a device-resident grad_x; both timed with HIP events around K calls after W warm-up calls
@@ -10,7 +10,9 @@ backward = one BatchModel.backward on a device-resident grad_x; both timed with 
 created with ns_max = NS_SOFT: the SOFT instantiations of the adjoint kernel, with qsoft / usoft / usoft_id written.
 --nullspace: on the same positive definite batch, BatchModel.backward(nullspace="all") -- every problem through the null-space
 kernel (daqp_batch_backward_nullspace, which = 1) -- timed next to the Gram adjoint and the forward step; the largest difference
-between the two adjoints, relative to the max norm of the Gram adjoint's [dz; dnu], goes into the record."""
+between the two adjoints, relative to the max norm of the Gram adjoint's [dz; dnu], goes into the record.
+--dual: on the same batch, BatchModel.backward(g, grad_lam=g_lam) -- daqp_batch_backward_dual, which = -1: the Gram adjoint with g_lam
+on the working set in the second block of its right-hand side -- timed next to the plain adjoint and the forward step."""
 import argparse
 import json
 import os
@@ -41,13 +43,14 @@ def main():
     ap.add_argument("--configs", default="C2,C3")
     ap.add_argument("--soft", action="store_true")
     ap.add_argument("--nullspace", action="store_true")
+    ap.add_argument("--dual", action="store_true")
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "backward_bench.jsonl"))
     a = ap.parse_args()
-    if a.soft and a.nullspace:
-        ap.error("--nullspace does not take soft rows")
+    if a.soft and (a.nullspace or a.dual):
+        ap.error("--nullspace and --dual do not take soft rows")
     import torch
     import daqp_amd
     from daqp_amd.synthetic import generate_batch_torch
@@ -89,6 +92,12 @@ def main():
             extra = dict(nullspace=True, nullspace_ms=round(ns_ms, 4), nullspace_over_backward=round(ns_ms / bwd_ms, 4),
                          nullspace_over_forward=round(ns_ms / fwd_ms, 4), nullspace_qps_per_s=round(N / ns_ms * 1e3),
                          nullspace_status_ok=int((o2["status"] == 0).sum()), nullspace_max_rel_diff=float((diff / scale)[both].max()))
+        if a.dual:
+            gl = torch.randn(N, m, dtype=torch.float64, device="cuda")
+            o3 = bm.backward(g, grad_lam=gl)
+            dual_ms = timed(lambda: bm.backward(g, grad_lam=gl), a.steps, a.warmup)
+            extra.update(dual=True, dual_ms=round(dual_ms, 4), dual_over_backward=round(dual_ms / bwd_ms, 4),
+                         dual_over_forward=round(dual_ms / fwd_ms, 4), dual_status_ok=int((o3["status"] == 0).sum()))
         rec = dict(tool="bench_backward", config=cfg, N=N, n=n, m=m, ms=ms, n_active=nact, steps=a.steps, warmup=a.warmup,
                    forward_ms=round(fwd_ms, 4), forward_setup_kernels_ms=round(setup_ms, 4), forward_solve_kernels_ms=round(solve_ms, 4),
                    backward_ms=round(bwd_ms, 4), backward_over_forward=round(bwd_ms / fwd_ms, 4),
