@@ -569,7 +569,9 @@ class EliminatedBatchModel:
     .flags (N,) int32 after setup / update: 1, -6 (dependent equality rows) or -8 (bupper != blower on an equality row); such a
     problem comes back with that exit flag and zero x, lam -- the rest of the batch is untouched.  Inputs are numpy arrays (copied) or
     device tensors (used in place: they must stay alive and unchanged while the model is in use -- expansion reads H, f and A).
-    settings: a dict of DAQP settings.  backward / refine / qp_layer do not go through an eliminated model: basis() gives x0, Z, c0."""
+    settings: a dict of DAQP settings.  backward() is the adjoint of the full problem at its full working set (the equality rows and
+    the active kept rows), solved on the two kept factors: qp_layer(..., eq_rows=...) is built on it.  Not built: refine through an
+    eliminated model, the adjoint with SOFT rows (ns_max > 0), shared H / A, per-problem equality sets; basis() gives x0, Z, c0."""
 
     def __init__(self, N, n, m, ms, eq_rows, ns_max=0, settings=None, device=None):
         self.N, self.n, self.m, self.ms, self.ns = N, n, m, ms, ns_max
@@ -713,6 +715,49 @@ class EliminatedBatchModel:
         """the reduced batch back to empty working sets: the next solve is a cold one"""
         self.reduced.reset()
         return self
+
+    def backward(self, grad_x, grad_lam=None, out=None, nullspace=False):
+        """The adjoint of the last solve in the full space (daqp_batch_eliminate_backward, include/daqp_amd.h): for grad_x = dl/dx
+        (N, n) and grad_lam = dl/dlam (N, m) -- either may be None (= 0), not both -- returns dict(dz, dbupper, dblower, status)
+        with BatchModel.backward's meaning and formulas, x and lam being those of solve().  The multiplier gradient of an
+        equality row comes back in dbupper (dblower is 0 there).  status (N,) int32: 0, the elimination flag (-6, -8) or why the
+        reduced problem has no derivative; the outputs of such a problem are zero.  Gradients are numpy arrays or device tensors;
+        out: 'torch' (device tensors, nothing waits for the device) or 'numpy' (default: what the gradients are).  nullspace
+        (False, True, "all") selects `which` = -1, 0, 1 of the reduced adjoint: an LP batch or a singular H_r needs True, nr <= 64.
+        Raises unless the last operation on the model was a successful solve(); models with ns_max > 0 are refused."""
+        if not self._el:
+            raise RuntimeError("EliminatedBatchModel.backward called before setup")
+        if nullspace not in (False, True, "all"):
+            raise ValueError('nullspace must be False, True or "all"')
+        if grad_x is None and grad_lam is None:
+            raise ValueError("grad_x and grad_lam are both None: there is nothing to differentiate")
+        N, n, m = self.N, self.n, self.m
+        if out is None:
+            out = "torch" if any(_is_torch(a) and a.is_cuda for a in (grad_x, grad_lam)) else "numpy"
+        if out == "torch":
+            dev = torch.device("cuda", self.device)
+            conv = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+            ptr = lambda a: None if a is None else a.data_ptr()
+            f64, i32, mem = torch.float64, torch.int32, MEM_DEVICE
+        else:
+            conv = lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64)
+            new = lambda shape, dtype: np.empty(shape, dtype)
+            ptr = lambda a: None if a is None else a.ctypes.data
+            f64, i32, mem = np.float64, np.int32, MEM_HOST
+        g, gl = conv(grad_x), conv(grad_lam)
+        if g is not None and tuple(g.shape) != (N, n):
+            raise ValueError(f"grad_x must have shape {(N, n)}")
+        if gl is not None and tuple(gl.shape) != (N, m):
+            raise ValueError(f"grad_lam must have shape {(N, m)}")
+        o = dict(dz=new((N, n), f64), dbupper=new((N, m), f64), dblower=new((N, m), f64), status=new((N,), i32))
+        which = -1 if nullspace is False else (1 if nullspace == "all" else 0)
+        rc = lib().daqp_batch_eliminate_backward(self._el, self.reduced._h, ptr(g), ptr(gl), ptr(o["dz"]), ptr(o["dbupper"]), ptr(o["dblower"]),
+                                                 ptr(o["status"]), which, mem)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_eliminate_backward failed ({rc}): {_lib.last_error()}")
+        self._bw_keep = [[g, gl], o]      # the launches read / write them after this call has returned
+        return o
 
     def certify(self, res, out=None):
         """certify_batch on the caller's FULL problem and res["x"], res["lam"] of a solve()"""

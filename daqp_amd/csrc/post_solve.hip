@@ -10,6 +10,7 @@
 #include "refine.hip.h"
 #include "refine_nullspace.hip.h"
 #include "eliminate.hip.h"
+#include "eliminate_adjoint.hip.h"
 
 namespace daqp_amd {
 // the adjoint kernel: backward_kernel.hip
@@ -41,6 +42,14 @@ extern template __global__ void k_elim_basis<1>(ElimDev, double *);
 extern template __global__ void k_elim_basis<2>(ElimDev, double *);
 extern template __global__ void k_elim_basis<4>(ElimDev, double *);
 extern template __global__ void k_elim_basis<8>(ElimDev, double *);
+extern template __global__ void k_adjoint_reduce<1>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_reduce<2>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_reduce<4>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_reduce<8>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_expand<1>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_expand<2>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_expand<4>(ElimDev, ElimAdjointArgs);
+extern template __global__ void k_adjoint_expand<8>(ElimDev, ElimAdjointArgs);
 }
 
 // What daqp_batch_eliminate keeps: the caller's problem (device pointers: borrowed, or the handle's own copies of host arrays), the
@@ -53,6 +62,10 @@ struct DAQPBatchElimination {
     unsigned long long bytes = 0;
     double *own_f = nullptr, *own_bu = nullptr, *own_bl = nullptr;      // the handle's copies of host-resident f / bounds
     int grid = 0;      // workgroup tier: persistent blocks, one n x n scratch matrix each
+    // daqp_batch_eliminate_backward's intermediates, allocated by its first call: grad_y, dz_r [N][nr], grad_lam_r, dbupper_r,
+    // dblower_r [N][mr], dz0 [N][n], status_r [N]
+    double *adj_gy = nullptr, *adj_glr = nullptr, *adj_dz0 = nullptr, *adj_dzr = nullptr, *adj_dbur = nullptr, *adj_dblr = nullptr;
+    int *adj_str = nullptr;
 };
 
 using namespace daqp_amd;
@@ -517,6 +530,62 @@ int daqp_batch_elimination_read(DAQPBatchElimination *el, c_float *H, c_float *f
     if (sense && mr) HIPCHK(hipMemcpyAsync(sense, d.senser, sizeof(int) * N * mr, kind, el->stream));
     if (memory == DAQP_MEM_HOST) HIPCHK(hipStreamSynchronize(el->stream));
     return 0;
+}
+
+// The adjoint of an eliminated batch (include/daqp_amd.h, eliminate_adjoint.hip.h): reduce the right-hand side, the adjoint of the
+// reduced batch (backward_launch on the handle's device buffers: it only enqueues), expand -- three launches on the handle's stream
+// (four where `which` == 0 adds the null-space kernel).  Every refusal, backward_launch's own included, comes before the first launch.
+int daqp_batch_eliminate_backward(DAQPBatchElimination *el, DAQPBatch *reduced, const c_float *grad_x, const c_float *grad_lam,
+                                  c_float *dz, c_float *dbupper, c_float *dblower, int *status, int which, int memory)
+{
+    const char *who = "daqp_batch_eliminate_backward";
+    int ndev = 0;
+    if (elim_no_device(&ndev)) return DAQP_EXIT_UNSUPPORTED;
+    if (!el || !reduced || !dz || !dbupper || !dblower || !status) { set_err("%s: null handle, batch or output array", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (!grad_x && !grad_lam) { set_err("%s: grad_x and grad_lam are both null: there is nothing to differentiate", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (which < -1 || which > 1) { set_err("%s: which must be -1 (Gram only), 0 (null space for the proximal problems) or 1 (null space for every problem)", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("%s: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE", who); return DAQP_EXIT_UNSUPPORTED; }
+    const ElimDev &d = el->d;
+    const BatchDev &rb = reduced->d;
+    if (rb.N != d.N || rb.n != d.nr || rb.m != d.mr || rb.ms != 0) {
+        set_err("%s: the reduced batch has shape (N, n, m, ms) = (%d, %d, %d, %d), the handle's reduced problem (%d, %d, %d, 0)", who, rb.N, rb.n, rb.m, rb.ms, d.N, d.nr, d.mr);
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (reduced->device != el->device) { set_err("%s: the reduced batch is on device %d, the handle on device %d", who, reduced->device, el->device); return DAQP_EXIT_UNSUPPORTED; }
+    if (reduced->stream != el->stream) { set_err("%s: the reduced batch and the handle are on different streams: the three launches are ordered by sharing one", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (reduced->ns_max > 0) { set_err("%s: reduced batches created with ns_max > 0 (soft constraints) are not supported: a SOFT kept row is weighted by the reduced q_k", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (which == 1 && d.nr > 64) { set_err("%s: which == 1 needs nr <= 64 (nr = %d): the null-space kernel holds a problem in one wavefront", who, d.nr); return DAQP_EXIT_UNSUPPORTED; }
+    if (!reduced->is_setup || !reduced->solved || reduced->pending_mask) {
+        set_err("%s: the last operation on the reduced batch was not a successful daqp_batch_solve", who);
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (which >= 0 && rb.H == nullptr) { set_err("%s: the reduced batch has no Hessian of the handle's to read", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (which != 1 && !pick_tier(rb.n, rb.cap, backward_lds_bytes).fits) { set_err("%s: nr = %d with working sets of %d rows does not fit the adjoint kernel", who, rb.n, rb.cap); return DAQP_EXIT_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(el->device));
+    const size_t N = d.N, n = d.n, m = d.m, nr = d.nr, mr = d.mr;
+    if (!el->adj_str) {
+        if (elim_alloc(el, &el->adj_gy, N * nr) || elim_alloc(el, &el->adj_glr, N * mr) || elim_alloc(el, &el->adj_dz0, N * n) ||
+            elim_alloc(el, &el->adj_dzr, N * nr) || elim_alloc(el, &el->adj_dbur, N * mr) || elim_alloc(el, &el->adj_dblr, N * mr) ||
+            elim_alloc(el, &el->adj_str, N))
+            return DAQP_EXIT_UNSUPPORTED;
+    }
+    ElimAdjointArgs a{};
+    a.grad_y = el->adj_gy; a.grad_lam_r = el->adj_glr; a.dz0 = el->adj_dz0;
+    a.dz_r = el->adj_dzr; a.dbu_r = el->adj_dbur; a.dbl_r = el->adj_dblr; a.status_r = el->adj_str;
+    Staging st(nullptr, nullptr, el->stream, memory);
+    if (st.in(&a.grad_x, 0, grad_x, N * n) || st.in(&a.grad_lam, 1, grad_lam, N * m) || st.out(&a.dz, 2, dz, N * n) ||
+        st.out(&a.dbupper, 3, dbupper, N * m) || st.out(&a.dblower, 4, dblower, N * m) || st.out(&a.status, 5, status, N))
+        return DAQP_EXIT_UNSUPPORTED;
+    void (*kr)(ElimDev, ElimAdjointArgs) = elim_pick(d.n, k_adjoint_reduce<1>, k_adjoint_reduce<2>, k_adjoint_reduce<4>, k_adjoint_reduce<8>);
+    hipLaunchKernelGGL(kr, dim3(d.N), dim3(64), 0, el->stream, d, a);
+    HIPCHK(hipGetLastError());
+    if (backward_launch(who, reduced, a.grad_y, a.dz_r, a.dbu_r, a.dbl_r, nullptr, nullptr, nullptr, a.status_r, DAQP_MEM_DEVICE, which,
+                        grad_lam ? a.grad_lam_r : nullptr))
+        return DAQP_EXIT_UNSUPPORTED;
+    void (*ke)(ElimDev, ElimAdjointArgs) = elim_pick(d.n, k_adjoint_expand<1>, k_adjoint_expand<2>, k_adjoint_expand<4>, k_adjoint_expand<8>);
+    hipLaunchKernelGGL(ke, dim3(d.N), dim3(64), 0, el->stream, d, a);
+    HIPCHK(hipGetLastError());
+    return st.finish();
 }
 
 unsigned long long daqp_batch_elimination_bytes(const DAQPBatchElimination *el) { return el ? el->bytes : 0; }

@@ -27,13 +27,19 @@ no solve (envelope theorem) and is added in torch:
 
     dl/df += g_fval x      dl/dH += 1/2 g_fval x x'      dl/dbupper_i, dl/dblower_i += -g_fval lam_i (the row's side)      dl/dA_i += g_fval lam_i x'
 
+qp_layer(..., eq_rows=[...]) names the equality rows of C = [first ms rows of I; A] (one ascending set for the batch, bupper == blower
+there): forward is an EliminatedBatchModel -- the rows are eliminated on the device, the reduced batch solved, the result expanded --
+and backward is ONE daqp_batch_eliminate_backward call: the KKT system of the full problem at its full working set, solved on the
+factor of the equality rows and the factor of the reduced Hessian (include/daqp_amd.h).  The formulas above are unchanged.  Every
+bound gradient of an equality row -- its multiplier gradient and the -g_fval lam term -- goes to bupper; blower gets zero there.
+
 Out of scope: gradients of soft_slack, lam or fval of batches with SOFT rows, per-row soft weights, proximal problems with n > 64 or
-with SOFT rows, an LP with one shared A.
+with SOFT rows, an LP with one shared A; with eq_rows: SOFT rows and one shared H / A.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
-from .api import INF, UPDATE_unconstrained, BatchModel
+from .api import INF, UPDATE_unconstrained, BatchModel, EliminatedBatchModel
 
 SOFT = 8      # DAQP_SOFT (include/daqp_amd.h)
 
@@ -229,11 +235,105 @@ class _QPLayer(torch.autograd.Function):
         return gH, gf, gA, gbu, gbl, None, None, None, None, None, None, None, None
 
 
+class _EliminatedQPLayer(torch.autograd.Function):
+    """qp_layer(..., eq_rows=...): forward through an EliminatedBatchModel, backward through its adjoint"""
+
+    @staticmethod
+    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, nullspace, returns, eq_rows):
+        if not f.is_cuda:
+            raise ValueError("qp_layer needs its inputs on the GPU")
+        N, n = f.shape
+        m = bupper.shape[1]
+        mA = 0 if A is None else A.shape[-2]
+        ms = m - mA if ms is None else int(ms)
+        if ms + mA != m:
+            raise ValueError(f"m = {m} bounds for ms = {ms} simple bounds and {mA} rows of A")
+        c = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
+        bl = torch.full_like(bupper, -INF).detach() if blower is None else blower
+        if sense is not None:
+            sense = torch.as_tensor(sense).detach().to(device=f.device, dtype=torch.int32)
+            if sense.dim() == 1:
+                sense = sense.expand(N, m)
+            if tuple(sense.shape) != (N, m):
+                raise ValueError(f"sense must have shape {(N, m)} or {(m,)}")
+            sense = sense.contiguous()
+        with torch.cuda.device(f.device):      # the model takes that device's current stream
+            em = EliminatedBatchModel(N, n, m, ms, eq_rows, 0, settings=dict(settings), device=f.device.index)
+            em.setup(c(H), c(f), c(A), c(bupper), c(bl), sense, init_mask=UPDATE_unconstrained)
+            r = em.solve(out="torch")
+        ctx.em, ctx.x, ctx.lam = em, r["x"], r["lam"]
+        ctx.ms, ctx.strict, ctx.info, ctx.nullspace = ms, strict, info, bool(nullspace)
+        ctx.returns, ctx.exitflag = returns, r["exitflag"]
+        ctx.eq = torch.as_tensor(em.eq_rows, dtype=torch.long, device=f.device)
+        if info is not None:
+            info["exitflag"] = r["exitflag"]
+            info["lam"] = r["lam"]
+        ctx.set_materialize_grads(False)
+        return tuple(r[k].clone() for k in returns)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        em, x, lam, ms = ctx.em, ctx.x, ctx.lam, ctx.ms
+        g = dict(zip(ctx.returns, grads))
+        c = lambda t: None if t is None else t.to(torch.float64).contiguous()
+        gx, gl, gv = c(g.get("x")), c(g.get("lam")), c(g.get("fval"))
+        none = (None,) * 13
+        if gx is None and gl is None and gv is None:
+            return none
+        o = None
+        if gx is not None or gl is not None:
+            with torch.cuda.device(x.device):
+                o = em.backward(gx, grad_lam=gl, out="torch", nullspace=ctx.nullspace)
+        # (no launch: the envelope terms exist wherever the solve ended optimal)
+        status = o["status"] if o is not None else torch.where(ctx.exitflag == 1, torch.zeros_like(ctx.exitflag), ctx.exitflag)
+        if ctx.info is not None:
+            ctx.info["status"] = status
+        if ctx.strict:
+            badq = torch.nonzero(status).flatten()
+            if badq.numel():
+                q = int(badq[0])
+                raise RuntimeError(f"qp_layer: {badq.numel()} of {em.N} problems have no derivative (first: problem {q}, status "
+                                   f"{int(status[q])}); strict=False gives them zero gradients")
+        need = ctx.needs_input_grad
+        gH = gf = gA = gbu = gbl = None
+        add = lambda a, b: b if a is None else a + b
+        if o is not None:
+            dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
+            if need[0]:
+                gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
+            if need[1]:
+                gf = -dz
+            if need[2]:
+                lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
+                gA = -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
+            if need[3]:
+                gbu = dbu
+            if need[4]:
+                gbl = dbl
+        if gv is not None:
+            gv = gv * (status == 0)      # a problem without a derivative gets zero gradients here as well
+            if need[0]:
+                gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
+            if need[1]:
+                gf = add(gf, gv[:, None] * x)
+            if need[2]:
+                lg = gv[:, None] * lam[:, ms:]
+                gA = add(gA, lg[:, :, None] * x[:, None, :])
+            up, lo = lam.clamp(min=0.0), lam.clamp(max=0.0)      # lam_i > 0: the row sits at its upper bound;
+            up[:, ctx.eq], lo[:, ctx.eq] = lam[:, ctx.eq], 0.0     # an equality row: everything to bupper
+            if need[3]:
+                gbu = add(gbu, -gv[:, None] * up)
+            if need[4]:
+                gbl = add(gbl, -gv[:, None] * lo)
+        return gH, gf, gA, gbu, gbl, None, None, None, None, None, None, None, None
+
+
 RETURNS = ("x", "lam", "fval")
 
 
 def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, nullspace=False, returns="x",
-             **settings):
+             eq_rows=None, **settings):
     """x* (N, n) of  min 1/2 x'Hx + f'x  s.t.  blower <= [x[:ms]; A x] <= bupper  for N problems, differentiable.
 
     H (N, n, n), f (N, n), A (N, mA, n) or None, bupper / blower (N, m) with m = ms + mA (ms defaults to m - mA; blower None =
@@ -259,8 +359,30 @@ def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sens
     multipliers lam (N, m) (> 0 at an upper bound, < 0 at a lower one, 0 off the working set) and fval (N,) = 1/2 x'Hx + f'x.
     Backward is one daqp_batch_backward_dual launch for the gradients through x and lam; the gradient through fval is added in
     torch without a solve.  With a gradient through fval alone nothing is launched and status is 0 wherever the solve ended
-    optimal.  Not with SOFT rows."""
+    optimal.  Not with SOFT rows.
+
+    eq_rows: a list or array of equality rows of [first ms rows of I; A] -- ONE ascending set of 1 .. n-1 indices for the whole batch,
+    bupper == blower there.  Forward goes through EliminatedBatchModel (the rows eliminated on the device, the reduced batch of n - neq
+    variables solved, the result expanded), backward is one daqp_batch_eliminate_backward call; returns, strict, info and nullspace
+    work as without it, nullspace being applied to the reduced problem (n - neq <= 64; H=None: an LP batch, differentiable at a vertex
+    of the reduced problem).  info["status"] is the elimination flag (-6: dependent equality rows, -8: bupper != blower on one) where
+    that is negative.  EVERY BOUND GRADIENT OF AN EQUALITY ROW GOES TO bupper -- the multiplier gradient dnu_E and the -g_fval lam_E
+    term of a gradient through fval -- and blower gets zero there: an equality right-hand side that feeds both bounds receives their
+    sum, which is its gradient.  Raises ValueError for H or A of one shared plant (2-D) and for SOFT rows.  Without eq_rows the layer
+    is what it was."""
     has_soft = sense is not None and bool(((torch.as_tensor(sense) & SOFT) != 0).any())
+    if eq_rows is not None:
+        if has_soft:
+            raise ValueError("qp_layer: eq_rows does not take SOFT rows: a SOFT kept row is weighted by the reduced q_k")
+        if (H is not None and H.dim() == 2) or (A is not None and A.dim() == 2):
+            raise ValueError("qp_layer: eq_rows does not take one shared H / A: the elimination needs H (N, n, n) and A (N, mA, n)")
+        if rho_soft is not None:
+            raise ValueError("qp_layer: eq_rows does not take rho_soft: there are no SOFT rows to weigh")
+        names = (returns,) if isinstance(returns, str) else tuple(returns)
+        if not names or len(set(names)) != len(names) or any(k not in RETURNS for k in names):
+            raise ValueError(f'qp_layer: returns must be "x" or distinct names out of {RETURNS} (got {returns!r})')
+        out = _EliminatedQPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, nullspace, names, eq_rows)
+        return out[0] if isinstance(returns, str) else out
     if nullspace and has_soft:
         raise ValueError("qp_layer: nullspace=True does not take SOFT rows")
     if isinstance(returns, str) and returns == "x":

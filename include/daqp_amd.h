@@ -497,7 +497,7 @@ int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *
  * NULL, which is outside -1..1, which == 1 with n > 64, the last operation on the batch was not a successful daqp_batch_solve, or the
  * batch was created with ns_max > 0.
  * Not built: soft rows (ns_max > 0 is refused), soft_slack gradients, Jacobians and multi-RHS solves, n > 64 on the null-space
- * route, EliminatedBatchModel, MultiBatchModel. */
+ * route, MultiBatchModel.  An eliminated batch (EliminatedBatchModel) has its own entry: daqp_batch_eliminate_backward. */
 int daqp_batch_backward_dual(DAQPBatch *b, const c_float *grad_x /* N*n, may be NULL = 0 */,
                              const c_float *grad_lam /* N*m, may be NULL = 0 */,
                              c_float *dz, c_float *dbupper, c_float *dblower, int *status,
@@ -593,8 +593,8 @@ int daqp_certify_batch(DAQPBatchCertificate *out, const DAQPBatchProblem *p, con
  * Every entry returns 0, or nonzero with the reason in daqp_amd_last_error() and no device work: neq < 1 or neq >= n; rows out of
  * range or not ascending; n > 511; a NULL pointer; host and device memory mixed within one call.  Without a HIP device every entry
  * returns DAQP_EXIT_UNSUPPORTED ("no HIP device").  A failed daqp_batch_eliminate leaves *out NULL.
- * Not built: DAQP_UPDATE_eliminate in place, per-problem equality sets, shared H / A, the multi-device entry, and backward / refine
- * through an eliminated batch. */
+ * Not built: DAQP_UPDATE_eliminate in place, per-problem equality sets, shared H / A, the multi-device entry, and refine through
+ * an eliminated batch.  The adjoint: daqp_batch_eliminate_backward below. */
 typedef struct DAQPBatchElimination DAQPBatchElimination;
 int daqp_batch_eliminate(DAQPBatchElimination **out, const DAQPBatchProblem *p, const int *eq_rows /* host, neq */, int neq,
                          const DAQPSettings *settings, int device, void *hip_stream);
@@ -606,6 +606,52 @@ int daqp_batch_elimination_basis(DAQPBatchElimination *el, c_float *x0 /* N*n */
 int daqp_batch_elimination_read(DAQPBatchElimination *el, c_float *H, c_float *f, c_float *A, c_float *bupper, c_float *blower, int *sense, int memory);
 unsigned long long daqp_batch_elimination_bytes(const DAQPBatchElimination *el);
 void daqp_batch_elimination_free(DAQPBatchElimination *el);
+/* The adjoint of an eliminated batch (eliminate_adjoint.hip.h): implicit differentiation needs neither dZ nor dx0, only the KKT system
+ * of the FULL problem at its full working set W = E u W_I -- E the equality rows, W_I the active kept rows of the reduced solve -- and
+ * that system is solved by the route of the forward pass, on the factor of the equality rows that the handle keeps and on the factor of
+ * H_r that the reduced batch keeps.  Notation of daqp_batch_eliminate: C = [first ms rows of I; A]; E = C_eq_rows with unit-row QR
+ * E' = Q [R; 0], Q = [Q1 Z], row norms s; I the kept rows; H_r = Z'HZ, A_r = C_I Z; W_I the stored working set of the reduced batch, its
+ * rows mapped back through the kept rows.  For g_x = dl/dx (grad_x: N*n, may be NULL = 0) and g_lam = dl/dlam (grad_lam: N*m, may be
+ * NULL = 0, read on W only; not both NULL) the call solves
+ *
+ *        [ H     E'   C_WI' ] [ dz    ]   [ g_x     ]
+ *        [ E     0    0     ] [ dnu_E ] = [ g_lam_E ]
+ *        [ C_WI  0    0     ] [ dnu_I ]   [ g_lam_WI]
+ *
+ * in three steps:
+ *   1. reduce (one kernel)   y = R^-T (g_lam_E / s),  dz0 = Q [y; 0],  grad_y = (Q'(g_x - H dz0))[neq:],
+ *                            grad_lam_r = g_lam_I - C_I dz0 for every kept row (the reduced adjoint reads it on W_I only).
+ *                            With grad_lam == NULL: dz0 = 0, grad_y = (Q'g_x)[neq:], and no grad_lam_r is formed.
+ *   2. solve                 the adjoint of the reduced batch -- what daqp_batch_backward_dual runs for it -- on grad_y and, when
+ *                            grad_lam was given, grad_lam_r; `which` is passed through unchanged: dz_r, dbupper_r, dblower_r, status_r
+ *   3. expand (one kernel)   dz = dz0 + Q [0; dz_r];  dnu_I = dbupper_r + dblower_r, written to the original row positions, each on
+ *                            the side where the reduced call put it;  R dnu~ = (Q'(g_x - H dz - C_WI' dnu_I))[:neq],  dnu_E = dnu~ / s
+ * -- the structure of the forward pass with e -> g_lam_E, f -> -g_x and the bounds -> g_lam_I.
+ *   - dnu_E goes to DBUPPER of the equality rows (the elimination reads e from bupper); dblower is 0 there.  A caller whose equality
+ *     right-hand side feeds both bounds adds the two, as the chain rule does.
+ *   - An LP batch (H == NULL) has H = 0 in every product.
+ *   - A problem whose elimination flag is -6 or -8 gets that flag as its status and zero outputs; every other problem gets status_r
+ *     (the rules of daqp_batch_backward / _nullspace on the reduced batch), with zero outputs where that is non-zero.
+ * dz (N*n), dbupper, dblower (N*m) and status (N) mean exactly what they mean for daqp_batch_backward: THE FIVE GRADIENT FORMULAS ARE
+ * UNCHANGED -- dl/df = -dz, dl/dH = -1/2 (dz x' + x dz'), dl/dA_i = -(lam_i dz + dnu_i x)' for the general rows i in W, dl/dbupper =
+ * dbupper, dl/dblower = dblower -- with the full x and lam that daqp_batch_expand returned, and so are the envelope terms of a gradient
+ * through fval (daqp_batch_backward_dual).
+ * `reduced` is the batch that was set up on daqp_batch_elimination_problem and solved.  Three launches on the handle's stream (one more
+ * where which == 0 adds the null-space kernel).  The intermediates (grad_y, grad_lam_r, dz0, dz_r, dbupper_r, dblower_r, status_r) are
+ * device buffers of the handle's, allocated at the first call and counted by daqp_batch_elimination_bytes from then on.  `memory`
+ * applies to all six arrays: with device memory the call only enqueues, with host memory it stages them and returns when the results
+ * are there.  H and A are read where daqp_batch_eliminate found them: borrowed device arrays must still be valid and unchanged.
+ * Returns nonzero, with the reason in the last-error string and without any device work, for
+ *   - a NULL handle, batch or output; both gradients NULL; which outside -1..1;
+ *   - a reduced batch whose (N, n, m, ms) is not (N, nr, mr, 0), or one on another device or another stream than the handle;
+ *   - a reduced batch created with ns_max > 0 (a SOFT kept row is weighted by the reduced q_k: out of scope);
+ *   - a reduced batch whose last operation was not a successful daqp_batch_solve;
+ *   - which == 1 with nr > 64.
+ * Not built: SOFT rows, refine through an eliminated batch, shared H / A, per-problem equality sets, the multi-device entry. */
+int daqp_batch_eliminate_backward(DAQPBatchElimination *el, DAQPBatch *reduced,
+                                  const c_float *grad_x /* N*n, may be NULL = 0 */, const c_float *grad_lam /* N*m, may be NULL = 0 */,
+                                  c_float *dz, c_float *dbupper, c_float *dblower, int *status,
+                                  int which /* -1, 0, 1: as daqp_batch_backward_dual, applied to the reduced batch */, int memory);
 /* one-shot: create + setup(DAQP_UPDATE_unconstrained) + solve + free == N x daqp_quadprog */
 int daqp_quadprog_batch(DAQPBatchResult *r, const DAQPBatchProblem *p, const DAQPSettings *settings);
 

@@ -3,7 +3,11 @@ expand, and of setup + solve of the unreduced batch on the same data, then the w
 in, device tensors out; each step timed on the host around a device synchronisation, best of --reps.  eliminate_s is the cold
 daqp_batch_eliminate call of a new handle: its device allocations are in the figure.  Prints one JSON line.
 
-    python tools/bench_eliminate.py [--N 2048] [--reps 3]
+--backward: behind the cold solves, the adjoint of both on the same (g_x, g_lam): EliminatedBatchModel.backward (reduce, the adjoint of
+the reduced batch, expand) next to BatchModel.backward of the unreduced model -- one untimed call each first (it allocates the
+intermediates), then the timed one.
+
+    python tools/bench_eliminate.py [--N 2048] [--reps 3] [--backward]
 """
 import argparse
 import json
@@ -48,6 +52,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--N", type=int, default=2048)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--backward", action="store_true")
     a = ap.parse_args()
     sync = torch.cuda.synchronize
     rows = []
@@ -55,6 +60,10 @@ def main():
         N = a.N if n <= 64 else max(64, a.N // 8)
         dev = [torch.as_tensor(v, device="cuda") for v in make(n, neq, m, N, 7)]
         best = {}
+        gen = torch.Generator(device="cuda").manual_seed(11)
+        gx = torch.randn(N, n, dtype=torch.float64, device="cuda", generator=gen)
+        gl = torch.randn(N, m, dtype=torch.float64, device="cuda", generator=gen)
+        derr = None
         for _ in range(a.reps):
             em = daqp_amd.EliminatedBatchModel(N, n, m, 0, np.arange(neq))
             bm = daqp_amd.BatchModel(N, n, m, 0)
@@ -65,6 +74,12 @@ def main():
             t["expand_s"], full = timed(lambda: em.expand(r, "torch"), sync)
             t["unreduced_setup_s"], _ = timed(lambda: bm.setup(*dev), sync)
             t["unreduced_solve_s"], ref = timed(lambda: bm.solve(out="torch"), sync)
+            if a.backward:
+                em.backward(gx, grad_lam=gl), bm.backward(gx, grad_lam=gl)
+                t["eliminated_backward_s"], o = timed(lambda: em.backward(gx, grad_lam=gl), sync)
+                t["unreduced_backward_s"], oref = timed(lambda: bm.backward(gx, grad_lam=gl), sync)
+                derr = float((o["dz"] - oref["dz"]).abs().max() / oref["dz"].abs().max())
+                ok_bw = bool((o["status"] == 0).all() and (oref["status"] == 0).all())
             # the warm path: new f on the kept factors (handle and reduced batch / unreduced batch), then a warm solve
             f2 = dev[1] * 1.01
             t["warm_update_s"], _ = timed(lambda: em.update(f=f2), sync)
@@ -81,7 +96,7 @@ def main():
         wel, wun = best["warm_update_s"] + best["warm_solve_expand_s"], best["unreduced_warm_update_s"] + best["unreduced_warm_solve_s"]
         rows.append(dict(n=n, neq=neq, m=m, N=N, **{k: round(v, 6) for k, v in best.items()}, eliminated_qps=round(N / el, 1),
                          unreduced_qps=round(N / un, 1), eliminated_warm_qps=round(N / wel, 1), unreduced_warm_qps=round(N / wun, 1),
-                         max_abs_dx=err, flags_equal=ok))
+                         max_abs_dx=err, flags_equal=ok, **(dict(backward_rel_ddz=derr, backward_status_zero=ok_bw) if a.backward else {})))
     print(json.dumps(dict(bench="eliminate", shapes=rows)))
 
 
