@@ -77,6 +77,7 @@ EXPORTS = [
     "daqp_batch_eliminate", "daqp_batch_eliminate_update", "daqp_batch_elimination_problem", "daqp_batch_elimination_flags", "daqp_batch_expand",
     "daqp_batch_elimination_basis", "daqp_batch_elimination_read", "daqp_batch_elimination_bytes", "daqp_batch_elimination_free",
     "daqp_batch_eliminate_backward",
+    "daqp_amd_describe_plan", "daqp_batch_describe",
     "daqp_batch_enable_trace", "daqp_batch_read_trace", "daqp_batch_enable_profile", "daqp_batch_read_profile", "daqp_batch_read_ldp",
 ]
 
@@ -85,8 +86,8 @@ EXPORTS = [
 # object was compiled with other flags)
 UNITS = {
     "daqp_amd.hip": ["daqp_amd.hip", "kernels.hip.h", "wave_ldp.hip.h", "wave_ldp_reg.hip.h", "setup_fast.hip.h", "prox.hip.h",
-                     "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h", "host.hip.h"],
-    "post_solve.hip": ["post_solve.hip", "host.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "refine_nullspace.hip.h", "eliminate.hip.h", "eliminate_adjoint.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
+                     "wg_layout.hip.h", "batch_dev.hip.h", "recheck.hip.h", "minrep.hip.h", "setup_m.hip.h", "setup_fact.hip.h", "reg_kernel.hip.h", "tiny_setup.hip.h", "setup_blk.hip.h", "multi.hip.h", "host.hip.h", "plan.hip.h"],
+    "post_solve.hip": ["post_solve.hip", "host.hip.h", "plan.hip.h", "wg_layout.hip.h", "backward.hip.h", "nullspace.hip.h", "certify.hip.h", "refine.hip.h", "refine_nullspace.hip.h", "eliminate.hip.h", "eliminate_adjoint.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "eliminate_kernel.hip": ["eliminate_kernel.hip", "eliminate.hip.h", "eliminate_adjoint.hip.h", "nullspace.hip.h", "batch_dev.hip.h", "wave_ldp.hip.h"],
     "reg_kernel.hip": ["reg_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
     "reg32_kernel.hip": ["reg32_kernel.hip", "reg_kernel.hip.h", "wave_ldp_reg.hip.h", "wave_ldp.hip.h", "batch_dev.hip.h"],
@@ -333,6 +334,8 @@ def lib():
     L.daqp_batch_eliminate_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci]
     L.daqp_batch_elimination_free.argtypes = [vp]
     L.daqp_batch_elimination_free.restype = None
+    L.daqp_amd_describe_plan.argtypes = [ci] * 9 + [C.c_char_p, ci]
+    L.daqp_batch_describe.argtypes = [vp, C.c_char_p, ci]
     L.reset_daqp_workspace.argtypes = [vp]
     L.reset_daqp_workspace.restype = None
     L.daqp_deactivate_constraints.argtypes = [vp]

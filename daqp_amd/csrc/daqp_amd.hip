@@ -24,7 +24,6 @@
 #include "tiny_setup.hip.h"
 #include "setup_blk.hip.h"
 #include "minrep.hip.h"
-#include "host.hip.h"
 // the workgroup-per-problem solve kernel lives in its own translation unit (wg_kernel.hip): a change to it does not rebuild
 // everything else
 namespace daqp_amd {
@@ -73,6 +72,8 @@ extern template __global__ void k_ldp_wg<2, true>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, false>(BatchDev, int);
 extern template __global__ void k_ldp_wg<4, true>(BatchDev, int);
 }
+#define DAQP_AMD_PLAN_KERNELS   // plan.hip.h with its kernel tables, behind the declarations above
+#include "host.hip.h"
 
 using namespace daqp_amd;
 
@@ -169,178 +170,114 @@ int push_descriptor(DAQPBatch *b)
     return 0;
 }
 
-typedef void (*ldp_kernel_t)(BatchDev, int);
-typedef void (*ldp_reg_kernel_t)(const BatchDev *, int);
-// register-resident variants: (row blocks, k-pairs) held per lane; needs cap <= 64 and L/rows in LDS
-struct RegShape { int nb, np; };
-#ifdef DAQP_AMD_FEW_VARIANTS   // development builds: fewer instantiations, faster compile
-const RegShape kRegShapes[] = {{1, 6}, {1, 8}, {3, 25}};
-#else
-const RegShape kRegShapes[] = {{1, 6}, {1, 8}, {1, 13}, {1, 16}, {2, 16}, {3, 8}, {4, 8}, {1, 25}, {3, 25}, {2, 32}};   // ((3,8), (4,8): few variables, many rows -- n <= 16, m <= 192; (1,25): n <= 50 with m <= 64 -- both at two waves per SIMD)
-#endif
-// the shapes served by an fp32 image ALONE (no full-register kernel exists: M itself would not fit 512 registers), first fit:
-// (4,32) n <= 63, m <= 256 | (8,16) n <= 32, m <= 512 | (6,25) n <= 50, m <= 384 | (5,32) n <= 63, m <= 320 -- 256 ... 320 image registers, one wave per SIMD
-const RegShape kImgOnlyShapes[] = {{4, 32}, {8, 16}, {6, 25}, {5, 32}};
-ldp_reg_kernel_t pick_img_only(const DAQPBatch *b)
+// one launch on the batch's stream; attr != 0: the kernel's limit of dynamic LDS is raised to that many bytes first
+template <class K, class A>
+int launch(DAQPBatch *b, K k, int grid, int threads, size_t lds, const A &arg, int mode, size_t attr = 0)
 {
-    if (b->io_nb == 4 && b->io_np == 32) return k_ldp_reg<4, 32, true, 1>;
-    if (b->io_nb == 8 && b->io_np == 16) return k_ldp_reg<8, 16, true, 1>;
-    if (b->io_nb == 6 && b->io_np == 25) return k_ldp_reg<6, 25, true, 1>;
-    if (b->io_nb == 5 && b->io_np == 32) return k_ldp_reg<5, 32, true, 1>;
-    return nullptr;
+    if (attr) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, b->stream, arg, mode);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
-// exact: the reference's arithmetic (two roundings per multiply-add); otherwise fused multiply-adds (default mode)
-ldp_reg_kernel_t pick_ldp_reg_img(const DAQPBatch *b)
-{
-    if (b->NB == 3 && b->NP == 25) return b->img_kind == 2 ? k_ldp_reg<3, 25, true, 2>      // (IMG = 2: the third row block holds at most 32 rows)
-                                                            : k_ldp_reg<3, 25, true, 1>;     // (161 <= m <= 192: three full blocks, 150 image registers, 23 of the rest in scratch)
-    if (b->NB == 2 && b->NP == 32) return k_ldp_reg<2, 32, true, 1>;    // (51 <= n <= 63, m <= 128: two full row blocks, 128 image registers)
-    return nullptr;
-}
-ldp_reg_kernel_t pick_ldp_reg(const DAQPBatch *b, bool exact)
-{
-#define DAQP_REG_PICK(nb, np) if (b->NB == nb && b->NP == np) return exact ? k_ldp_reg<nb, np, false> : k_ldp_reg<nb, np, true>;
-    DAQP_REG_PICK(1, 6)
-    DAQP_REG_PICK(1, 8)
-    DAQP_REG_PICK(3, 25)
-#ifndef DAQP_AMD_FEW_VARIANTS
-    DAQP_REG_PICK(1, 13)
-    DAQP_REG_PICK(1, 16)
-    DAQP_REG_PICK(2, 16)
-    DAQP_REG_PICK(3, 8)
-    DAQP_REG_PICK(4, 8)
-    DAQP_REG_PICK(1, 25)
-    DAQP_REG_PICK(2, 32)
-#endif
-#undef DAQP_REG_PICK
-    return nullptr;
-}
-ldp_kernel_t pick_ldp(const DAQPBatch *b)
-{
-    const int C = b->C;
-    const bool spill = b->spill;
-#ifdef DAQP_AMD_FEW_VARIANTS
-    if (!spill) return k_ldp<4, false, 0, 0>;
-    return C == 8 ? k_ldp<8, true, 0, 0> : k_ldp<4, true, 0, 0>;
-#else
-    if (!spill) {
-        if (C == 1) return k_ldp<1, false, 0, 0>;
-        if (C == 2) return k_ldp<2, false, 0, 0>;
-        return k_ldp<4, false, 0, 0>;
-    }
-    if (C == 1) return k_ldp<1, true, 0, 0>;
-    if (C == 2) return k_ldp<2, true, 0, 0>;
-    if (C == 8) return k_ldp<8, true, 0, 0>;
-    return k_ldp<4, true, 0, 0>;
-#endif
-}
+#define LAUNCH(...) do { if (launch(__VA_ARGS__)) return DAQP_EXIT_UNSUPPORTED; } while (0)
 
+// the solve launch(es) of the batch's shape: which ones is pick_path's choice (plan.hip.h), here is what each path sends
 int launch_ldp(DAQPBatch *b, int mode, bool descriptor_changed = true)
 {
-    if (b->use_wg) {
+    (void)descriptor_changed;
+    const SolvePlan &p = b->plan;
+    const int N = b->d.N;
+    // problems that run the proximal outer loop keep the reference's arithmetic in both modes (their setup passes do as well)
+    const bool exact_kernels = b->d.exact_setup != 0 || b->in_prox_loop || b->exact_sticky;
+    bool img_allowed = true;
+    if (p.img32 && !exact_kernels) {
+        if (b->img_ho_pin && (long long)*b->img_ho_pin * 2 > N && (++b->img_skipped & 15) != 0) img_allowed = false;
+        if (img_allowed && (mode & 3) == 2 && N < p.img_min_warm) img_allowed = false;      // (a warm step is short: the crossover sits higher)
+    }
+    const SolvePath path = pick_path(p, mode, exact_kernels, b->fresh, img_allowed);
+    const ldp_kernel_t kf = pick_ldp(p);
+    const BatchDev *dp = b->d_dev;
+    switch (path) {
+    case kPathWg: case kPathWgTier: {
         // persistent workgroups pull problems from a counter; whatever outgrows the LDS-resident L is flagged and solved by
         // the one-wave kernel right behind (mode | 4: flagged problems only -- an empty pass costs a few microseconds)
         typedef void (*wg_kernel_t)(BatchDev, int);
         BatchDev dd = b->d;
         if (b->in_prox_loop || b->exact_sticky) dd.exact_setup = 1;   // problems of the proximal outer loop keep the reference's arithmetic in both modes
-        wg_kernel_t kw = dd.exact_setup ? (b->wg_C == 2 ? k_ldp_wg<2, true> : k_ldp_wg<4, true>) : (b->wg_C == 2 ? k_ldp_wg<2, false> : k_ldp_wg<4, false>);
+        wg_kernel_t kw = dd.exact_setup ? (p.wg_C == 2 ? k_ldp_wg<2, true> : k_ldp_wg<4, true>) : (p.wg_C == 2 ? k_ldp_wg<2, false> : k_ldp_wg<4, false>);
         int wg_mode = mode;
-        if (b->wg_tier_grid > 0 && b->fresh && mode == 0 && !dd.exact_setup) {
+        if (path == kPathWgTier) {
             // a first solve in the default arithmetic: two four-wave workgroups per CU, the inverse factor tiered (LDS + the problem's slot of the
             // stored factor); what it flags -- warm working sets, soft rows, a factor that left the inverse representation -- is solved by the
             // launch behind it, which holds the whole factor in LDS
             HIPCHK(hipMemsetAsync(b->d.wg_counter, 0, sizeof(int), b->stream));
-            wg_kernel_t kt = b->wg_C == 2 ? k_ldp_wg<2, false, true> : k_ldp_wg<4, false, true>;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_wg_tier));
-            hipLaunchKernelGGL(kt, dim3(b->wg_tier_grid), dim3(256), b->lds_wg_tier, b->stream, dd, mode);
-            HIPCHK(hipGetLastError());
+            wg_kernel_t kt = p.wg_C == 2 ? k_ldp_wg<2, false, true> : k_ldp_wg<4, false, true>;
+            LAUNCH(b, kt, p.wg_tier_grid, 256, p.lds_wg_tier, dd, mode, p.lds_wg_tier);
             wg_mode = mode | 4;
         }
         HIPCHK(hipMemsetAsync(b->d.wg_counter, 0, sizeof(int), b->stream));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_wg));
-        hipLaunchKernelGGL(kw, dim3(b->wg_grid), dim3(64 * b->wg_W), b->lds_wg, b->stream, dd, wg_mode);
-        HIPCHK(hipGetLastError());
-        ldp_kernel_t kf = pick_ldp(b);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_ldp));
-        hipLaunchKernelGGL(kf, dim3(b->d.N), dim3(64), b->lds_ldp, b->stream, b->d, mode | 4);
-        HIPCHK(hipGetLastError());
+        LAUNCH(b, kw, p.wg_grid, 64 * p.wg_W, p.lds_wg, dd, wg_mode, p.lds_wg);
+        LAUNCH(b, kf, N, 64, p.lds_ldp, b->d, mode | 4, p.lds_ldp);
         return 0;
     }
-    if (b->NB > 0) {
-        // problems that run the proximal outer loop keep the reference's arithmetic in both modes (their setup passes do as well)
-        const bool exact_kernels = b->d.exact_setup != 0 || b->in_prox_loop || b->exact_sticky;
-        ldp_reg_kernel_t kr = pick_ldp_reg(b, exact_kernels);
+    case kPathReg: case kPathRegImg: case kPathN64ImgOnly: case kPathRegHandover: {
+        ldp_reg_kernel_t kr = pick_ldp_reg(p, exact_kernels);
         // the descriptor travels through device memory: stream-ordered copy, then the launch
-        (void)descriptor_changed;
         if (push_descriptor(b)) return DAQP_EXIT_UNSUPPORTED;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_ldp));
-        bool use_img = b->img32 && !exact_kernels;
-        if (use_img && b->img_ho_pin && (long long)*b->img_ho_pin * 2 > b->d.N && (++b->img_skipped & 15) != 0) use_img = false;
-        if (use_img && (mode & 3) == 2 && b->d.N < b->img_min_warm) use_img = false;      // (a warm step is short: the crossover sits higher)
-        if (use_img) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_ldp));
+        if (path == kPathRegImg) {
             // the image kernel first (two waves per SIMD); the problems whose working set outgrows its LDS are flagged and solved, from the
             // state they were stored in, by the full-register kernel right behind (mode | 4: flagged problems only)
-            ldp_reg_kernel_t ki = pick_ldp_reg_img(b);
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(b->lds_img > b->lds_img_warm ? b->lds_img : b->lds_img_warm)));
-            const bool warm = (mode & 3) == 2 && b->img_rows_warm > 0;
-            const size_t lds = warm ? b->lds_img_warm : b->lds_img;
+            ldp_reg_kernel_t ki = pick_ldp_reg_img(p);
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(p.lds_img > p.lds_img_warm ? p.lds_img : p.lds_img_warm)));
+            const bool warm = (mode & 3) == 2 && p.img_rows_warm > 0;
             if (b->d.img_ho) HIPCHK(hipMemsetAsync(b->d.img_ho, 0, sizeof(int), b->stream));
-            HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)b->d.N * sizeof(int), b->stream));      // (the kernels only ever SET a flag)
-            hipLaunchKernelGGL(ki, dim3(b->d.N), dim3(64), lds, b->stream, (const BatchDev *)b->d_dev, warm ? (mode | b->img_rows_warm << 16 | b->img_cache_warm << 22) : mode);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(kr, dim3(b->d.N), dim3(64), b->lds_ldp, b->stream, (const BatchDev *)b->d_dev, mode | 4);
-            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)N * sizeof(int), b->stream));      // (the kernels only ever SET a flag)
+            LAUNCH(b, ki, N, 64, warm ? p.lds_img_warm : p.lds_img, dp, warm ? (mode | p.img_rows_warm << 16 | p.img_cache_warm << 22) : mode);
+            LAUNCH(b, kr, N, 64, p.lds_ldp, dp, mode | 4);
             if (b->d.img_ho && (mode & 3) != 1) HIPCHK(hipMemcpyAsync(b->img_ho_pin, b->d.img_ho, sizeof(int), hipMemcpyDeviceToHost, b->stream));
             return 0;
         }
-        if (b->reg_handover && b->img_only && mode == 0 && !exact_kernels) {
+        if (path == kPathN64ImgOnly) {
             // n = 64 in the default arithmetic: the image-only kernel (64 rows held), k_ldp behind it for the problems that need a 65th row
-            ldp_reg_kernel_t ki = pick_img_only(b);
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_img));
-            HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)b->d.N * sizeof(int), b->stream));
-            hipLaunchKernelGGL(ki, dim3(b->d.N), dim3(64), b->lds_img, b->stream, (const BatchDev *)b->d_dev, mode);
-            HIPCHK(hipGetLastError());
-            ldp_kernel_t kf = pick_ldp(b);
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_fb));
-            hipLaunchKernelGGL(kf, dim3(b->d.N), dim3(64), b->lds_fb, b->stream, b->d, mode | 4);
-            HIPCHK(hipGetLastError());
+            ldp_reg_kernel_t ki = pick_img_only(p);
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_img));
+            HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)N * sizeof(int), b->stream));
+            LAUNCH(b, ki, N, 64, p.lds_img, dp, mode);
+            LAUNCH(b, kf, N, 64, p.lds_fb, b->d, mode | 4, p.lds_fb);
             return 0;
         }
-        if (b->reg_handover) HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)b->d.N * sizeof(int), b->stream));
-        hipLaunchKernelGGL(kr, dim3(b->d.N), dim3(64), b->lds_ldp, b->stream, (const BatchDev *)b->d_dev, mode);
-        HIPCHK(hipGetLastError());
-        if (b->reg_handover) {   // the problems it flagged (mode | 4: nobody else is touched; an empty pass costs a few microseconds)
+        if (p.reg_handover) HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)N * sizeof(int), b->stream));
+        LAUNCH(b, kr, N, 64, p.lds_ldp, dp, mode);
+        if (path == kPathRegHandover) {   // the problems it flagged (mode | 4: nobody else is touched; an empty pass costs a few microseconds)
             if ((mode & 3) == 2) { set_err("fused update + solve launch on a hand-over shape"); return DAQP_EXIT_UNSUPPORTED; }
             BatchDev dd = b->d;
             if (b->in_prox_loop || b->exact_sticky) dd.exact_setup = 1;
-            ldp_kernel_t kf = pick_ldp(b);
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_fb));
-            hipLaunchKernelGGL(kf, dim3(b->d.N), dim3(64), b->lds_fb, b->stream, dd, mode | 4);
-            HIPCHK(hipGetLastError());
+            LAUNCH(b, kf, N, 64, p.lds_fb, dd, mode | 4, p.lds_fb);
         }
         return 0;
     }
-    ldp_kernel_t k = pick_ldp(b);
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_ldp));
-    if (b->img_only && mode == 0 && !b->d.exact_setup && !b->in_prox_loop && !b->exact_sticky) {
-        // The shapes whose M fits no register file but whose fp32 IMAGE does (kImgOnlyShapes): the image kernel alone at one wave per SIMD --
-        // the scan runs out of registers instead of streaming 8 (m - ms) n bytes per iteration from L2 / HBM --, and this kernel behind it for
-        // whatever it flags (mode | 4; the image kernel holds every working-set row the shape can have, so that is an empty pass)
-        if (push_descriptor(b)) return DAQP_EXIT_UNSUPPORTED;
-        ldp_reg_kernel_t ki = pick_img_only(b);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_img));
-        if (b->d.img_ho) HIPCHK(hipMemsetAsync(b->d.img_ho, 0, sizeof(int), b->stream));
-        HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)b->d.N * sizeof(int), b->stream));
-        hipLaunchKernelGGL(ki, dim3(b->d.N), dim3(64), b->lds_img, b->stream, (const BatchDev *)b->d_dev, mode);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k, dim3(b->d.N), dim3(64), b->lds_ldp, b->stream, b->d, mode | 4);
-        HIPCHK(hipGetLastError());
+    case kPathWave: case kPathWaveImgOnly:
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_ldp));
+        if (path == kPathWaveImgOnly) {
+            // The shapes whose M fits no register file but whose fp32 IMAGE does (kImgOnlyShapes): the image kernel alone at one wave per SIMD --
+            // the scan runs out of registers instead of streaming 8 (m - ms) n bytes per iteration from L2 / HBM --, and this kernel behind it for
+            // whatever it flags (mode | 4; the image kernel holds every working-set row the shape can have, so that is an empty pass)
+            if (push_descriptor(b)) return DAQP_EXIT_UNSUPPORTED;
+            ldp_reg_kernel_t ki = pick_img_only(p);
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_img));
+            if (b->d.img_ho) HIPCHK(hipMemsetAsync(b->d.img_ho, 0, sizeof(int), b->stream));
+            HIPCHK(hipMemsetAsync(b->d.fallback, 0, (size_t)N * sizeof(int), b->stream));
+            LAUNCH(b, ki, N, 64, p.lds_img, dp, mode);
+            LAUNCH(b, kf, N, 64, p.lds_ldp, b->d, mode | 4);
+            return 0;
+        }
+        LAUNCH(b, kf, N, 64, p.lds_ldp, b->d, mode);
         return 0;
     }
-    hipLaunchKernelGGL(k, dim3(b->d.N), dim3(64), b->lds_ldp, b->stream, b->d, mode);
-    HIPCHK(hipGetLastError());
     return 0;
 }
+#undef LAUNCH
 
 // a deferred daqp_batch_update is applied now by the stand-alone kernel (someone wants to see the state before a solve)
 int flush_update(DAQPBatch *b)
@@ -348,7 +285,7 @@ int flush_update(DAQPBatch *b)
     if (!b->pending_mask) return 0;
     const int mask = b->pending_mask;
     b->pending_mask = 0;
-    hipLaunchKernelGGL(k_update, dim3(b->d.N), dim3(64), b->lds_update, b->stream, b->d, mask);
+    hipLaunchKernelGGL(k_update, dim3(b->d.N), dim3(64), b->plan.lds_update, b->stream, b->d, mask);
     HIPCHK(hipGetLastError());
     return launch_ldp(b, 1);
 }
@@ -395,7 +332,24 @@ setup_kernel_t pick_setup_fast(int n, bool fused)
 // serves every shape here (these updates are not on the path the configurations are timed on), always in the reference's arithmetic.
 setup_kernel_t pick_setup_part(const DAQPBatch *b)
 {
-    return b->setup_spill ? (b->d.n > 256 ? k_setup<true, 8, false, true> : k_setup<true, 4, false, true>) : k_setup<false, 4, false, true>;
+    return b->plan.setup_spill ? (b->d.n > 256 ? k_setup<true, 8, false, true> : k_setup<true, 4, false, true>) : k_setup<false, 4, false, true>;
+}
+// the setup kernel of a full setup and its LDS, for the batch's own descriptor or the one-problem descriptor of a shared factorisation: the
+// one-wave kernels of n <= 64 in the arithmetic of the moment, else the generic kernel (factors in LDS, or in scratch: setup_spill);
+// defer_m: the instantiation without the general rows (k_setup_m follows: more waves per SIMD), gs: with its factors in scratch
+setup_kernel_t pick_setup(const DAQPBatch *b, const BatchDev &d, bool defer_m, bool gs, size_t *lds)
+{
+    const SolvePlan &p = b->plan;
+    *lds = p.lds_setup;
+    if (defer_m) {
+        if (gs && !p.setup_spill) *lds = (size_t)setup_lds(d.n, d.m, true).total_bytes;
+        return gs ? k_setup<true, 4, true> : k_setup<false, 4, true>;
+    }
+    if (p.fast_setup) {
+        *lds = (size_t)fast_lds(d.n, d.m, d.exact_setup, d.mA).total_bytes;   // the MFMA path overlays the A tile on R^-1
+        return pick_setup_fast(d.n, d.exact_setup == 0);
+    }
+    return p.setup_spill ? (d.n > 256 ? k_setup<true, 8> : k_setup<true>) : k_setup<false>;
 }
 int read_counters(DAQPBatch *b)
 {
@@ -459,11 +413,11 @@ int regularise(DAQPBatch *b, BatchDev &d, int mask, bool lp, bool counted = fals
     HIPCHK(hipGetLastError());
     // the shifted passes keep M in the reference's operation order whatever the arithmetic mode of the batch (their
     // problems are then bit-identical to the reference in both modes); an LP's one pass is the generic kernel's diagonal path
-    const bool gs = b->setup_spill;
+    const bool gs = b->plan.setup_spill;
     setup_kernel_t ks = gs ? (d.n > 256 ? k_setup<true, 8> : k_setup<true>) : k_setup<false>;
     size_t lds = (size_t)setup_lds(d.n, d.m, gs).total_bytes;
     if (b->part_mask && !lp) ks = pick_setup_part(b);       // (a partial update's flagged problems: the kernel that knows which sense / bounds it took)
-    else if (b->fast_setup && !lp) {
+    else if (b->plan.fast_setup && !lp) {
         ks = (d.n <= 16) ? k_setup_fast<16, true> : (d.n <= 32 ? k_setup_fast<32, true> : (d.n <= 56 ? k_setup_fast<56, true> : k_setup_fast<64, true>));
         lds = (size_t)fast_lds(d.n, d.m, 1, d.mA).total_bytes;
     }
@@ -494,7 +448,7 @@ int regularise(DAQPBatch *b, BatchDev &d, int mask, bool lp, bool counted = fals
 bool defers_m(const DAQPBatch *b, const BatchDev &d)
 {
     static const bool off = [] { const char *e = getenv("DAQP_AMD_NO_SETUP_M"); return e && atoi(e) != 0; }();
-    return !off && !b->fast_setup && !d.exact_setup && d.setup_sq != nullptr && d.m_tick != nullptr && d.n <= 208 && d.mA > 0 && d.prox_pass == 0;
+    return !off && !b->plan.fast_setup && !d.exact_setup && d.setup_sq != nullptr && d.m_tick != nullptr && d.n <= 208 && d.mA > 0 && d.prox_pass == 0;
 }
 int launch_setup_m(DAQPBatch *b, const BatchDev &d)
 {
@@ -508,8 +462,8 @@ int launch_setup_m(DAQPBatch *b, const BatchDev &d)
 // daqp_update_ldp(mask within UPDATE_v|UPDATE_d) followed by daqp_solve, whichever kernels the shape uses
 int launch_update_solve(DAQPBatch *b, int mask, bool descriptor_changed)
 {
-    if (b->NB > 0 && !b->reg_handover) return launch_ldp(b, 2 | (mask << 4), descriptor_changed);
-    hipLaunchKernelGGL(k_update, dim3(b->d.N), dim3(64), b->lds_update, b->stream, b->d, mask);
+    if (b->plan.NB > 0 && !b->plan.reg_handover) return launch_ldp(b, 2 | (mask << 4), descriptor_changed);
+    hipLaunchKernelGGL(k_update, dim3(b->d.N), dim3(64), b->plan.lds_update, b->stream, b->d, mask);
     HIPCHK(hipGetLastError());
     if (launch_ldp(b, 1)) return DAQP_EXIT_UNSUPPORTED;
     return launch_ldp(b, 0);
@@ -533,9 +487,9 @@ int solve_with_prox(DAQPBatch *b, int mode, bool ordinary_done = false)
     int *o_flag = d.exitflag, *o_iter = d.iter;
     d.f = b->px.feff; d.fval = b->px.t_fval; d.soft = b->px.t_soft; d.exitflag = b->px.t_flag; d.iter = b->px.t_iter;
     const ProxOut po = {f_user, d.lam, o_fval, o_soft, o_flag, o_iter};
-    const size_t lds_grad = (size_t)ldp_lds(d.n, d.m, d.cap, b->spill).total_bytes;
+    const size_t lds_grad = (size_t)ldp_lds(d.n, d.m, d.cap, b->plan.spill).total_bytes;
     typedef void (*grad_kernel_t)(BatchDev, ProxDev, double *, ProxOut);
-    const grad_kernel_t kgrad = b->C == 8 ? k_lp_gradient<8, true> : (b->spill ? k_lp_gradient<4, true> : k_lp_gradient<4, false>);
+    const grad_kernel_t kgrad = b->plan.C == 8 ? k_lp_gradient<8, true> : (b->plan.spill ? k_lp_gradient<4, true> : k_lp_gradient<4, false>);
     if (b->px.lp) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kgrad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_grad));
     int rc = 0, outer = 0;
     b->in_prox_loop = true;
@@ -651,7 +605,7 @@ int recheck_infeasible(DAQPBatch *b)
     if (!b->redo) {
         DAQPBatch *rb = nullptr;
         // no memory for the companion: the first pass's verdicts stand (a valid solve does not fail over its second opinion)
-        if (daqp_batch_create(&rb, cap < 2 ? 2 : cap, d.n, d.m, d.ms, b->ns_max, &d.st, b->device)) { (void)hipGetLastError(); b->rechecked = -1; return 0; }
+        if (daqp_batch_create(&rb, cap < 2 ? 2 : cap, d.n, d.m, d.ms, b->plan.ns_max, &d.st, b->device)) { (void)hipGetLastError(); b->rechecked = -1; return 0; }
         rb->recheck = false;
         b->redo = rb;
     }
@@ -726,15 +680,6 @@ std::mutex g_pool_mu;
 std::vector<DAQPBatch *> g_pool;
 constexpr size_t kPoolMax = 8;
 bool pool_enabled() { const char *e = getenv("DAQP_AMD_NO_POOL"); return !(e && atoi(e) != 0); }
-std::string env_signature()
-{
-    static const char *names[] = {"DAQP_AMD_LDS_LIMIT", "DAQP_AMD_FORCE_SPILL", "DAQP_AMD_STREAM_M", "DAQP_AMD_NO_WG", "DAQP_AMD_WG_WAVES",
-                                  "DAQP_AMD_WG_CAPL", "DAQP_AMD_WG_GRID", "DAQP_AMD_NO_WG_TIER", "DAQP_AMD_WG_R0", "DAQP_AMD_WG_TIER_GRID", "DAQP_AMD_WG_TIER_MIN_BATCH", "DAQP_AMD_SLOW_SETUP", "DAQP_AMD_NO_SCAN32", "DAQP_AMD_WG_INVERSE", "DAQP_AMD_NO_TINY_SETUP", "DAQP_AMD_NO_RECHECK", "DAQP_AMD_NO_SETUP_M", "DAQP_AMD_NO_BLK_SETUP",
-                                  "DAQP_AMD_REG_ROWS", "DAQP_AMD_NO_REG_HANDOVER", "DAQP_AMD_NO_FACT_WG", "DAQP_AMD_NO_FACT_SMALL", "DAQP_AMD_NO_IMG32", "DAQP_AMD_IMG_ROWS", "DAQP_AMD_IMG_MIN_BATCH", "DAQP_AMD_IMG_WAVES", "DAQP_AMD_IMG_CACHE", "DAQP_AMD_IMG_WARM_ROWS", "DAQP_AMD_IMG_WARM_WAVES", "DAQP_AMD_NO_IMG_ONLY", "DAQP_AMD_IMG_ONLY_MIN_BATCH", "DAQP_AMD_NO_BLK_BOUNDS"};
-    std::string k;
-    for (const char *nme : names) { const char *v = getenv(nme); k += v ? v : "-"; k += '|'; }
-    return k;
-}
 void destroy_batch(DAQPBatch *b)
 {
     (void)hipSetDevice(b->device);
@@ -780,241 +725,86 @@ int daqp_batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, 
 {
     return batch_create(out, N, n, m, ms, ns_max, settings, device, 0);
 }
-static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, const DAQPSettings *settings, int device, int group)
+} // extern "C"
+namespace {
+// Stage 2 of the plan, for the shapes of the workgroup kernel: the device is asked for its CU count and for how the kernels fit a CU, plan.hip.h
+// decides.  The one thing decided here: a device whose k_ldp_wg refuses the plan's LDS leaves the shape to the one-wave kernel (use_wg = false).
+void plan_on_device(DAQPBatch *b, const Tuning &T)
 {
-    if (!out) return DAQP_EXIT_UNSUPPORTED;
-    *out = nullptr;
-    if (N <= 0 || n <= 0 || m < 0 || ms < 0 || ms > m || ms > n || ns_max < 0) {
-        set_err("bad dimensions N=%d n=%d m=%d ms=%d ns=%d", N, n, m, ms, ns_max);
-        return DAQP_EXIT_UNSUPPORTED;
+    SolvePlan &p = b->plan;
+    typedef void (*wg_kernel_t)(BatchDev, int);
+    wg_kernel_t kw = p.wg_C == 2 ? k_ldp_wg<2, false> : k_ldp_wg<4, false>;
+    wg_kernel_t kwx = p.wg_C == 2 ? k_ldp_wg<2, true> : k_ldp_wg<4, true>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kwx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_wg);
+    (void)hipGetLastError();
+    int cus = 0, per_cu = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device) != hipSuccess || cus <= 0) cus = 256;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_wg) != hipSuccess) {
+        (void)hipGetLastError();      // (not sticky: the next launch check must not report this)
+        p.use_wg = false;             // the kernel cannot be launched with this much LDS: the one-wave kernel takes the shape
     }
-    const int cap = n + ns_max + 1;
-    if (cap > 512 || n > 511) { set_err("n + ns + 1 = %d exceeds the 512-row working-set limit of this build", cap); return DAQP_EXIT_UNSUPPORTED; }
-    int ndev = 0;
-    const hipError_t dev_rc = hipGetDeviceCount(&ndev);
-    if (dev_rc == hipSuccess && ndev > 0 && device >= 0 && device < 64) {
-        // (registered AFTER the HIP runtime initialised itself -- the call above --, so it runs BEFORE that runtime's own exit handlers)
-        static std::once_flag once;
-        std::call_once(once, [] { if (!getenv("DAQP_AMD_NO_EXIT_SYNC")) atexit(daqp_amd_shutdown); });
-        g_devices_used.fetch_or(1ull << device);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kw), 64 * p.wg_W, p.lds_wg) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
     }
-    if (dev_rc != hipSuccess || ndev == 0) {
-        set_err("no HIP device: libdaqp_amd has no CPU path");
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    const std::string env_key = env_signature();
-    if (N == 1 && group <= 1 && pool_enabled()) {
-        DAQPBatch *hit = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(g_pool_mu);
-            for (size_t i = 0; i < g_pool.size(); ++i) {
-                DAQPBatch *c = g_pool[i];
-                if (c->device == device && c->d.n == n && c->d.m == m && c->d.ms == ms && c->ns_max == ns_max && c->env_key == env_key) {
-                    hit = c; g_pool.erase(g_pool.begin() + i); break;
-                }
-            }
-        }
-        if (hit) {
-            if (hipSetDevice(device) != hipSuccess) { destroy_batch(hit); set_err("hipSetDevice(%d) failed", device); return DAQP_EXIT_UNSUPPORTED; }
-            BatchDev &hd = hit->d;
-            if (settings) hd.st = *settings; else default_settings(&hd.st);
-            const char *ex = getenv("DAQP_AMD_EXACT");
-            hd.exact_setup = (ex && atoi(ex) != 0) ? 1 : 0;
-            // the iterate of the previous owner: gone (a fresh batch starts from zeros too)
-            if (put_async(hit->st_dev, hd.st, hit->stream) ||
-                hipMemsetAsync(hd.vecs, 0, (size_t)5 * hd.cap * sizeof(double), hit->stream) != hipSuccess ||
-                hipMemsetAsync(hd.qs, 0, sizeof(QState), hit->stream) != hipSuccess) { destroy_batch(hit); set_err("reset of a pooled workspace failed"); return DAQP_EXIT_UNSUPPORTED; }
-            hit->solved = false;
-            *out = hit;
-            return 0;
-        }
-    }
-    DAQPBatch *b = new DAQPBatch();
-    b->device = device;
-    b->env_key = env_key; b->ns_max = ns_max;
-    { const char *nr = getenv("DAQP_AMD_NO_RECHECK"); b->recheck = !(nr && atoi(nr) != 0); }
-    if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice(%d) failed", device); delete b; return DAQP_EXIT_UNSUPPORTED; }
+    b->dev_cus = cus; b->dev_per_cu = per_cu;
+    TierQuery q;
+    if (!plan_wg_grid(&p, T, cus, per_cu, &q)) return;
+    wg_kernel_t kt = p.wg_C == 2 ? k_ldp_wg<2, false, true> : k_ldp_wg<4, false, true>;
+    int per2 = 0;
+    const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds) == hipSuccess;
+    if (!attr_ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, reinterpret_cast<const void *>(kt), 256, q.lds) != hipSuccess) per2 = 0;
+    if (per2 < 2) (void)hipGetLastError();
+    b->dev_tier_attr_ok = attr_ok ? 1 : 0; b->dev_per_cu_tier = per2;
+    plan_wg_tier(&p, T, cus, q, attr_ok, per2);
+}
+
+// every buffer the plan names; what the kernels never write in full is zeroed once, right where it is allocated
+int allocate(DAQPBatch *b)
+{
+    const SolvePlan &p = b->plan;
     BatchDev &d = b->d;
-    d.N = N; d.n = n; d.m = m; d.ms = ms; d.cap = cap; d.mA = m - ms;
-    d.npair = (n + 1) / 2; d.nblk = (m + 63) / 64; d.ldr = n | 1; d.nquad = (d.npair + 1) / 2;
-    d.ltri = round_up(cap * (cap + 1) / 2, 2); d.rtri = n * (n + 1) / 2;   // even stride: 16-byte aligned rows for the direct HBM->LDS copy
-    if (settings) d.st = *settings; else default_settings(&d.st);
-    b->C = cap <= 64 ? 1 : (cap <= 128 ? 2 : (cap <= 256 ? 4 : 8));
-#ifdef DAQP_AMD_FEW_VARIANTS
-    if (b->C < 4) b->C = 4;
-#endif
-    const char *env = getenv("DAQP_AMD_LDS_LIMIT");
-    const int lds_limit = env ? atoi(env) : 80 * 1024;
-    b->spill = ldp_lds(n, m, cap, false).total_bytes > lds_limit;
-    if (getenv("DAQP_AMD_FORCE_SPILL") || cap > 256) b->spill = true;
-    if (!b->spill && cap <= 65 && !getenv("DAQP_AMD_STREAM_M"))
-        for (const RegShape &rs : kRegShapes)
-            if (d.nblk <= rs.nb && d.npair <= rs.np) { b->NB = rs.nb; b->NP = rs.np; break; }
-    // one lane per working-set row: 64 rows.  n = 64 without soft rows may hold 65 (only while a 65th constraint is being exchanged at a full
-    // vertex): the (2,32) shape takes it and hands the few problems that get there to k_ldp (launch_ldp); every other shape needs cap <= 64
-    d.reg_rows = 64;
-    if (const char *re = getenv("DAQP_AMD_REG_ROWS")) { const int v = atoi(re); if (v >= 1 && v < 64) d.reg_rows = v; }   // tests: force the hand-over
-    if (b->NB > 0 && d.reg_rows < cap) {
-        if (b->NB == 2 && b->NP == 32 && !getenv("DAQP_AMD_NO_REG_HANDOVER")) b->reg_handover = true;
-        else if (cap > 64) { b->NB = 0; b->NP = 0; }
-    }
-    if (b->reg_handover) b->lds_fb = (size_t)ldp_lds(n, m, cap, b->spill).total_bytes;
-    // The shapes whose M fills the register file (one wave per SIMD) run, in the default arithmetic and on batches that fill the device twice
-    // over, as an fp32 IMAGE of M at two waves per SIMD (reg_kernel.hip.h, IMG = 1).  Its LDS holds img_rows working-set rows (C2: the peak is
-    // 27 rows on average, above 40 on 1.3 % of the problems -- those are handed to the full-register kernel behind it)
-    b->img_kind = (b->NB == 3 && b->NP == 25) ? (m <= 160 ? 2 : 1) : ((b->NB == 2 && b->NP == 32) ? 1 : 0);
-    if (b->img_kind && cap <= 64 && !b->reg_handover && !getenv("DAQP_AMD_NO_IMG32")) {
-        int min_batch = 10240, rows = 42;      // (tools/img_threshold.py: below ~10 000 problems -- warm launches: ~16 000, see launch_ldp -- the device is not full twice over and a problem's latency decides: one wave per SIMD is faster per problem)
-        if (const char *e = getenv("DAQP_AMD_IMG_MIN_BATCH")) min_batch = atoi(e);
-        if (const char *e = getenv("DAQP_AMD_IMG_ROWS")) { const int v = atoi(e); if (v >= 2 && v <= 64) rows = v; }
-        if (getenv("DAQP_AMD_IMG_MIN_BATCH")) b->img_min_warm = min_batch;      // (the tests' override applies to every launch)
-        if (N >= min_batch) { b->img32 = true; d.img_rows = rows < cap ? rows : cap; }
-    }
-    d.ldrc = 0;
-    if (b->NB > 0) {   // stride == 2 (mod 4): rows 16-byte aligned and 16 consecutive rows hit 16 distinct 4-bank groups
-        int l = n > 2 * b->NP ? n : 2 * b->NP;
-        while ((l & 3) != 2) ++l;
-        d.ldrc = l;
-    }
-    b->lds_ldp = b->NB > 0 ? (size_t)reg_lds_bytes(b->NB, n, m, cap, d.ldrc) : (size_t)ldp_lds(n, m, cap, b->spill, d.ldrc).total_bytes;
-    // No register shape for (n, m), but the fp32 image of M fits one (kImgOnlyShapes: n <= 63 with m <= 256 ... 512, one wave per SIMD): the default
-    // arithmetic's solves run on it (launch_ldp); everything else about the batch stays the generic one-wave path's.  Every working-set row the
-    // shape can have is held (img_rows = cap), as many of them in LDS as leave four workgroups per CU, the rest in the scratch tier.
-    // (n <= 16: M streamed is as fast -- n = 8, m = 256: 0.86 against 1.02 ms per 20 000 -- a scan is 16 column pairs of L2 hits)
-    int io_nb = 0, io_np = 0;
-    for (const RegShape &rs : kImgOnlyShapes)
-        if (d.nblk <= rs.nb && d.npair <= rs.np) { io_nb = rs.nb; io_np = rs.np; break; }
-    // (cap = 65 is n = 64 without soft rows: a 65th row exists only while a constraint is exchanged at a full vertex -- the image kernel holds 64
-    //  and flags such a problem for k_ldp behind it, as the (2,32) registers do for m <= 128)
-    // (n = 64 with m <= 128 keeps its (2,32) registers for the exact mode, fused updates and one-problem calls; the default arithmetic's plain
-    //  solves of a batch take the image-only kernel there as well: 6.5 -> 4.0 ms per 20 000 at m = 128 -- the fp32 scan is half the issue slots)
-    const bool n64 = b->NB == 2 && b->NP == 32 && b->reg_handover && N > 1;
-    if ((b->NB == 0 || n64) && !b->spill && n > 16 && cap <= 65 && n <= 64 && io_nb > 0 && !getenv("DAQP_AMD_STREAM_M") && !getenv("DAQP_AMD_NO_IMG32") && !getenv("DAQP_AMD_NO_IMG_ONLY")) {
-        int min_batch = 1;
-        if (const char *e = getenv("DAQP_AMD_IMG_ONLY_MIN_BATCH")) min_batch = atoi(e);
-        if (N >= min_batch) {
-            b->img_only = true; b->io_nb = io_nb; b->io_np = io_np;
-            int l = n > 2 * io_np ? n : 2 * io_np;
-            while ((l & 3) != 2) ++l;
-            d.ldrc = l;                      // (the row-cache stride of the register kernels; k_ldp has its own)
-            d.img_rows = cap < 64 ? cap : 64;
-            const int budget = (160 * 1024 / 4) / 512 * 512;
-            int cache = d.img_rows;
-            while (cache > 2 && reg_img_lds_bytes(io_nb, 1, n, m, d.img_rows, cache, d.ldrc) > budget) --cache;
-            d.img_cache = cache;
-            b->lds_img = (size_t)reg_img_lds_bytes(io_nb, 1, n, m, d.img_rows, cache, d.ldrc);
-        }
-    }
-    if (b->img32) {
-        // rows of the active-row cache in LDS: as many as leave `waves` workgroups per CU (the rest of a working set lives in rowc_g, L2-resident);
-        // a workgroup's share of the CU's 160 KB is granted in 512-byte steps
-        int waves = 8;
-        if (const char *e = getenv("DAQP_AMD_IMG_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 8) waves = v; }
-        const int budget = (160 * 1024 / waves) / 512 * 512;
-        int cache = d.img_rows;
-        while (cache > 2 && reg_img_lds_bytes(b->NB, b->img_kind, n, m, d.img_rows, cache, d.ldrc) > budget) --cache;
-        if (const char *e = getenv("DAQP_AMD_IMG_CACHE")) { const int v = atoi(e); if (v >= 1) cache = v < d.img_rows ? v : d.img_rows; }
-        d.img_cache = cache;
-        b->lds_img = (size_t)reg_img_lds_bytes(b->NB, b->img_kind, n, m, d.img_rows, cache, d.ldrc);
-        if (!getenv("DAQP_AMD_IMG_ROWS") && !getenv("DAQP_AMD_IMG_CACHE")) {      // (the tests' overrides apply to every launch)
-            int wrows = 40;
-            if (const char *e = getenv("DAQP_AMD_IMG_WARM_ROWS")) wrows = atoi(e);
-            if (wrows >= 2 && wrows < d.img_rows) {
-                int wwaves = waves;
-                if (const char *e = getenv("DAQP_AMD_IMG_WARM_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 8) wwaves = v; }
-                const int wbudget = (160 * 1024 / wwaves) / 512 * 512;
-                int wc = wrows;
-                while (wc > 2 && reg_img_lds_bytes(b->NB, b->img_kind, n, m, wrows, wc, d.ldrc) > wbudget) --wc;
-                b->img_rows_warm = wrows; b->img_cache_warm = wc;
-                b->lds_img_warm = (size_t)reg_img_lds_bytes(b->NB, b->img_kind, n, m, wrows, wc, d.ldrc);
-            }
-        }
-    }
-    if (b->NB == 0 && !b->img_only && cap > 64 && cap <= 256 && !getenv("DAQP_AMD_NO_WG")) {     // (beyond 256 rows: the one-wave kernel with eight chunks, everything large in HBM scratch)
-        int W = d.nblk < 4 ? 4 : (d.nblk > kWgMaxWaves ? kWgMaxWaves : d.nblk);
-        const int lds_max = 160 * 1024 - 512;          // (the kernel's static LDS -- 320 bytes by the code generator's report -- comes on top of the
-                                                       //  dynamic allocation: with 256 bytes of reserve a shape whose packed factor ended within 64 bytes
-                                                       //  of the limit, (n, m) = (187, 371), could not be launched at all)
-        const int Cw = cap <= 128 ? 2 : 4;
-        // Two workgroups per CU beat one with more waves wherever the whole factor fits half the LDS: one problem's serial master phases then run
-        // under the other's bandwidth phases (n = 100, m = 300: solve launch 29.8 -> 17.9 ms per 4 096; n = 110, m = 330: 17.1 -> 10.8 ms,
-        // profiles/r06t_wg_two_per_cu.txt).  The register file holds eight waves per CU, so two workgroups means four waves each.
-        if (W > 4 && wg_lds_bytes(Cw, m, cap) <= lds_max / 2 - 256) W = 4;
-        if (const char *we = getenv("DAQP_AMD_WG_WAVES")) { const int v = atoi(we); if (v >= 4 && v <= kWgMaxWaves) W = v; }
-        int capL = cap;
-        while (capL > 16 && wg_lds_bytes(Cw, m, capL) > lds_max) --capL;
-        if (const char *ce = getenv("DAQP_AMD_WG_CAPL")) { const int v = atoi(ce); if (v >= 2 && v < capL) capL = v; }   // (tests: force the hand-over)
-        if (wg_lds_bytes(Cw, m, capL) <= lds_max && capL >= (cap < 48 ? cap : 48)) {
-            b->use_wg = true; b->wg_W = W; b->wg_C = Cw;
-            { const char *iv = getenv("DAQP_AMD_WG_INVERSE"); d.wg_inverse = (iv && atoi(iv) == 0) ? 0 : 1; }   // default mode: L^-1 instead of L (wg_ldp.hip.h)
-            d.wg_capL = capL; d.wg_capT = round_up(cap, 8);
-            b->lds_wg = (size_t)wg_lds_bytes(Cw, m, capL);
-        }
-    }
-    b->fast_setup = (n <= 64) && !getenv("DAQP_AMD_SLOW_SETUP");
-    b->tiny_setup = b->fast_setup && n <= TNC && m <= TMR && !getenv("DAQP_AMD_NO_TINY_SETUP");
-    {   // DAQP_AMD_EXACT=1: keep the reference's summation order in M = A R^-1 (bit-exact LDP); default: MFMA
-        const char *ex = getenv("DAQP_AMD_EXACT");
-        d.exact_setup = (ex && atoi(ex) != 0) ? 1 : 0;
-    }
-    b->setup_spill = !b->fast_setup && (setup_lds(n, m).total_bytes > 150 * 1024 || getenv("DAQP_AMD_FORCE_SPILL") || n > 256);
-    b->lds_setup = b->fast_setup ? (size_t)fast_lds(n, m, 1, m - ms).total_bytes : (size_t)setup_lds(n, m, b->setup_spill).total_bytes;
-    // 64 < n <= ~134: both factors fit the LDS of k_setup, where ONE wave factors and inverts in the reference's order -- 13.5 ms per 4 096 problems at
-    // n = 100 against 5.2 ms at n = 150, where k_fact_wg (a workgroup per problem, matrix cores) does it.  The default arithmetic's full setup takes
-    // k_fact_wg + the scratch variant of k_setup for these shapes too (profiles/r06v_shape_map.txt -> r06w); exact mode, partial updates and the
-    // regularising passes keep the LDS variant.
-    b->fact_gs = !b->fast_setup && !b->setup_spill && n > 64 && n <= kFactMaxN && !getenv("DAQP_AMD_NO_FACT_WG") && !getenv("DAQP_AMD_NO_FACT_SMALL");
-    b->lds_update = (size_t)round_up(n, 2) * 16;
-    if (b->lds_ldp > 160 * 1024 || b->lds_setup > 160 * 1024) {
-        set_err("problem too large for the LDS-staged setup (needs %zu / %zu bytes)", b->lds_setup, b->lds_ldp);
-        delete b;
-        return DAQP_EXIT_UNSUPPORTED;
-    }
-    const size_t Nn = (size_t)N;
-    const size_t Nf = group > 1 ? (size_t)((N + group - 1) / group) : Nn;      // sets of factors
+    const int n = p.n, m = p.m, cap = p.cap;
+    const size_t Nn = (size_t)p.N, Nf = (size_t)p.factor_sets;
     int rc = 0;
-    rc |= dev_alloc(b, &d.Mblk, Nf * d.nblk * d.npair * 128);
-    rc |= dev_alloc(b, &d.Rinv, Nf * d.rtri);
+    rc |= dev_alloc(b, &d.Mblk, Nf * p.nblk * p.npair * 128);
+    rc |= dev_alloc(b, &d.Rinv, Nf * p.rtri);
     rc |= dev_alloc(b, &d.v, Nn * n);
     rc |= dev_alloc(b, &d.scaling, Nf * m);
     rc |= dev_alloc(b, &d.dupper, Nn * m);
     rc |= dev_alloc(b, &d.dlower, Nn * m);
     rc |= dev_alloc(b, &d.sense, Nn * m);
     rc |= dev_alloc(b, &d.xunc, Nn * n);
-    rc |= dev_alloc(b, &d.L, Nn * d.ltri);
+    rc |= dev_alloc(b, &d.L, Nn * p.ltri);
     rc |= dev_alloc(b, &d.vecs, Nn * 5 * cap);
     rc |= dev_alloc(b, &d.WS, Nn * cap);
     rc |= dev_alloc(b, &d.qs, Nn);
-    if (b->spill) rc |= dev_alloc(b, &d.rowc_g, Nn * cap * d.ldr);
-    if (b->img_only && d.img_rows > d.img_cache) rc |= dev_alloc(b, &d.rowc_g, Nn * (size_t)((d.img_rows - d.img_cache) * d.ldrc));
-    if (b->img32) {
-        int t2 = d.img_rows - d.img_cache;
-        if (b->img_rows_warm - b->img_cache_warm > t2) t2 = b->img_rows_warm - b->img_cache_warm;
-        if (t2 > 0) rc |= dev_alloc(b, &d.rowc_g, Nn * (size_t)(t2 * d.ldrc));
+    if (p.spill) rc |= dev_alloc(b, &d.rowc_g, Nn * cap * p.ldr);
+    if (p.img_only && p.img_rows > p.img_cache) rc |= dev_alloc(b, &d.rowc_g, Nn * (size_t)((p.img_rows - p.img_cache) * p.ldrc));
+    if (p.img32) {
+        int t2 = p.img_rows - p.img_cache;
+        if (p.img_rows_warm - p.img_cache_warm > t2) t2 = p.img_rows_warm - p.img_cache_warm;
+        if (t2 > 0) rc |= dev_alloc(b, &d.rowc_g, Nn * (size_t)(t2 * p.ldrc));
     }
-    // (a grouped batch is never set up from H / A: the scratch of the QP setup kernels stays away)
-    if ((b->setup_spill || b->fact_gs) && group <= 1) rc |= dev_alloc(b, &d.setup_g, Nn * 2 * (size_t)round_up(d.rtri, 2));
-    // fp32 image of M for the workgroup kernel's screening scan (generic setup kernel only: it is the one that writes it)
-    if (b->use_wg && !b->fast_setup && !getenv("DAQP_AMD_NO_SCAN32")) {
-        const size_t cnt = Nf * (size_t)d.nblk * d.nquad * 256;
+    if (p.has_setup_g) rc |= dev_alloc(b, &d.setup_g, Nn * 2 * (size_t)round_up(p.rtri, 2));
+    if (p.has_m32) {
+        const size_t cnt = Nf * (size_t)p.nblk * p.nquad * 256;
         rc |= dev_alloc(b, &d.M32, cnt);
         if (!rc) HIPCHK(hipMemset(d.M32, 0, cnt * sizeof(float)));
     }
-    if (!b->fast_setup && group <= 1) {   // zeroed once: the kernel only ever writes the upper triangle
+    if (p.has_setup_sq) {   // zeroed once: the kernel only ever writes the upper triangle
         const size_t sq = Nn * (size_t)round_up(n, 32) * (size_t)round_up(n, 16);
         rc |= dev_alloc(b, &d.setup_sq, sq);
         if (!rc) HIPCHK(hipMemset(d.setup_sq, 0, sq * sizeof(double)));
         rc |= dev_alloc(b, &d.m_tick, Nn);
-        if ((b->setup_spill || b->fact_gs) && n <= kFactMaxN && !getenv("DAQP_AMD_NO_FACT_WG")) rc |= dev_alloc(b, &b->fact_buf, Nn * 4);
+        if (p.has_fact_buf) rc |= dev_alloc(b, &b->fact_buf, Nn * 4);
         if (!rc) HIPCHK(hipMemset(d.m_tick, 0, Nn * sizeof(int)));
     }
-    if (N == 1) {   // one slab: x[n] lam[m] fval soft | flag iter -- in mapped host memory, written by the solve kernel itself (see mapped_out)
+    if (p.N == 1) {   // one slab: x[n] lam[m] fval soft | flag iter -- in mapped host memory, written by the solve kernel itself (see mapped_out)
         double *slab = nullptr;
         b->out_bytes = ((size_t)n + m + 3) * sizeof(double);
         void *dp = nullptr;
-        static const bool no_map = [] { const char *e = getenv("DAQP_AMD_NO_MAPPED_RESULTS"); return e && atoi(e) != 0; }();
-        if (!no_map && hipHostMalloc(reinterpret_cast<void **>(&b->pin_out), b->out_bytes, hipHostMallocMapped) == hipSuccess &&
+        if (p.mapped_results && hipHostMalloc(reinterpret_cast<void **>(&b->pin_out), b->out_bytes, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer(&dp, b->pin_out, 0) == hipSuccess) {
             slab = static_cast<double *>(dp);
             memset(b->pin_out, 0, b->out_bytes);
@@ -1040,78 +830,101 @@ static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max
     rc |= dev_alloc(b, &b->st_dev, 1);
     rc |= dev_alloc(b, &b->d_dev, 1);
     rc |= dev_alloc(b, &b->px.counter, 4);
-    {   // period of the constant device clock behind s_memrealtime (settings->time_limit): asked of the runtime, not assumed
-        int khz = 0;
-        d.tick_s = (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) ? 1.0 / (1e3 * (double)khz) : 1e-8;
-        d.tstart = nullptr;
-    }
-    if (b->use_wg && !rc) {
-        typedef void (*wg_kernel_t)(BatchDev, int);
-        wg_kernel_t kw = b->wg_C == 2 ? k_ldp_wg<2, false> : k_ldp_wg<4, false>;
-        wg_kernel_t kwx = b->wg_C == 2 ? k_ldp_wg<2, true> : k_ldp_wg<4, true>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kwx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_wg);
-        (void)hipGetLastError();
-        int cus = 0, per_cu = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_wg) != hipSuccess) {
-            (void)hipGetLastError();      // (not sticky: the next launch check must not report this)
-            b->use_wg = false;            // the kernel cannot be launched with this much LDS: the one-wave kernel takes the shape
-        }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kw), 64 * b->wg_W, b->lds_wg) != hipSuccess || per_cu < 1) {
-            (void)hipGetLastError();
-            per_cu = 1;
-        }
-        long long g = (long long)cus * per_cu;
-        if (const char *ge = getenv("DAQP_AMD_WG_GRID")) { const long long v = atoll(ge); if (v >= 1) g = v; }   // tuning: problems in flight
-        b->wg_grid = (int)(g < N ? g : N);
-        // Tiered launch (wg_kernel.hip.h, TIER): where the whole factor allows only one workgroup per CU, cold solves run two four-wave workgroups
-        // per CU with the rows of the inverse factor beyond what half the LDS holds in HBM.  Worth it only while enough problems are in flight.
-        d.wg_r0 = 0;
-        long long tier_min = 2LL * cus;
-        if (const char *te = getenv("DAQP_AMD_WG_TIER_MIN_BATCH")) { const long long v = atoll(te); if (v >= 1) tier_min = v; }    // (tests: small batches through the tiered launch)
-        if (b->use_wg && per_cu == 1 && d.wg_inverse && !getenv("DAQP_AMD_NO_WG_TIER") && N >= tier_min) {
-            const int half = (160 * 1024 - 512) / 2 - 256;
-            wg_kernel_t kt = b->wg_C == 2 ? k_ldp_wg<2, false, true> : k_ldp_wg<4, false, true>;
-            int r0 = cap;
-            while (r0 > 16 && wg_lds_bytes(b->wg_C, m, r0) > half) --r0;
-            if (const char *re = getenv("DAQP_AMD_WG_R0")) { const int v = atoi(re); if (v >= 8 && v < r0) r0 = v; }    // (tests: more rows in the HBM tier)
-            int per2 = 0;
-            const size_t lds2 = (size_t)wg_lds_bytes(b->wg_C, m, r0);
-            if (r0 >= 32 && r0 < cap && hipFuncSetAttribute(reinterpret_cast<const void *>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) == hipSuccess
-                && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per2, reinterpret_cast<const void *>(kt), 256, lds2) == hipSuccess && per2 >= 2) {
-                d.wg_r0 = r0; b->lds_wg_tier = lds2;
-                long long g2 = (long long)cus * per2;
-                if (const char *ge = getenv("DAQP_AMD_WG_TIER_GRID")) { const long long v = atoll(ge); if (v >= 1) g2 = v; }
-                b->wg_tier_grid = (int)(g2 < N ? g2 : N);
-            } else (void)hipGetLastError();
-        }
-        const int wg_slots = b->wg_grid > b->wg_tier_grid ? b->wg_grid : b->wg_tier_grid;   // scratch per workgroup in flight, whichever launch has more
+    if (p.wg_W > 0 && !rc) {      // (the workgroup kernel's scratch: also where the device refused its LDS, use_wg = false)
+        const int wg_slots = p.wg_grid > p.wg_tier_grid ? p.wg_grid : p.wg_tier_grid;   // scratch per workgroup in flight, whichever launch has more
         rc |= dev_alloc(b, &d.wg_counter, 1);
         {   // row-major active rows per workgroup in flight, whole 32-column chunks per row; the pad columns are zero and stay zero
             const size_t cnt = (size_t)wg_slots * cap * wg_row_stride(n);
             rc |= dev_alloc(b, &d.wg_rowc, cnt);
             if (!rc && hipMemset(d.wg_rowc, 0, cnt * sizeof(double)) != hipSuccess) rc = 1;
         }
-        rc |= dev_alloc(b, &d.wg_rowcT, (size_t)wg_slots * n * d.wg_capT);
+        rc |= dev_alloc(b, &d.wg_rowcT, (size_t)wg_slots * n * p.wg_capT);
         rc |= dev_alloc(b, &d.fallback, Nn);
         if (!rc && hipMemset(d.fallback, 0, Nn * sizeof(int)) != hipSuccess) rc = 1;
     }
-    if (b->img32 && !rc) {
+    if (p.img32 && !rc) {
         rc |= dev_alloc(b, &d.img_ho, 1);
         if (!rc && hipHostMalloc(reinterpret_cast<void **>(&b->img_ho_pin), sizeof(int), hipHostMallocDefault) != hipSuccess) rc = 1;
         if (!rc) *b->img_ho_pin = 0;
     }
-    if ((b->reg_handover || b->img32 || b->img_only) && !rc) {
+    if ((p.reg_handover || p.img32 || p.img_only) && !rc) {
         rc |= dev_alloc(b, &d.fallback, Nn);
         if (!rc && hipMemset(d.fallback, 0, Nn * sizeof(int)) != hipSuccess) rc = 1;
     }
+    return rc;
+}
+} // namespace
+
+extern "C" {
+// validate, pool, plan (plan.hip.h: the shape, then the device's numbers), allocate, initialise
+static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max, const DAQPSettings *settings, int device, int group)
+{
+    if (!out) return DAQP_EXIT_UNSUPPORTED;
+    *out = nullptr;
+    char why[kPlanWhy];
+    if (!plan_dims_ok(N, n, m, ms, ns_max, why)) { set_err("%s", why); return DAQP_EXIT_UNSUPPORTED; }
+    int ndev = 0;
+    const hipError_t dev_rc = hipGetDeviceCount(&ndev);
+    if (dev_rc == hipSuccess && ndev > 0 && device >= 0 && device < 64) {
+        // (registered AFTER the HIP runtime initialised itself -- the call above --, so it runs BEFORE that runtime's own exit handlers)
+        static std::once_flag once;
+        std::call_once(once, [] { if (!getenv("DAQP_AMD_NO_EXIT_SYNC")) atexit(daqp_amd_shutdown); });
+        g_devices_used.fetch_or(1ull << device);
+    }
+    if (dev_rc != hipSuccess || ndev == 0) {
+        set_err("no HIP device: libdaqp_amd has no CPU path");
+        return DAQP_EXIT_UNSUPPORTED;
+    }
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    const Tuning T = read_tuning();
+    if (N == 1 && group <= 1 && pool_enabled()) {
+        DAQPBatch *hit = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(g_pool_mu);
+            for (size_t i = 0; i < g_pool.size(); ++i) {
+                DAQPBatch *c = g_pool[i];
+                if (c->device == device && c->d.n == n && c->d.m == m && c->d.ms == ms && c->plan.ns_max == ns_max && c->env_key == T.env_key) {
+                    hit = c; g_pool.erase(g_pool.begin() + i); break;
+                }
+            }
+        }
+        if (hit) {
+            if (hipSetDevice(device) != hipSuccess) { destroy_batch(hit); set_err("hipSetDevice(%d) failed", device); return DAQP_EXIT_UNSUPPORTED; }
+            BatchDev &hd = hit->d;
+            if (settings) hd.st = *settings; else default_settings(&hd.st);
+            hd.exact_setup = T.on(SW_EXACT) ? 1 : 0;      // (not part of the key: the workspace takes the arithmetic of the moment)
+            // the iterate of the previous owner: gone (a fresh batch starts from zeros too)
+            if (put_async(hit->st_dev, hd.st, hit->stream) ||
+                hipMemsetAsync(hd.vecs, 0, (size_t)5 * hd.cap * sizeof(double), hit->stream) != hipSuccess ||
+                hipMemsetAsync(hd.qs, 0, sizeof(QState), hit->stream) != hipSuccess) { destroy_batch(hit); set_err("reset of a pooled workspace failed"); return DAQP_EXIT_UNSUPPORTED; }
+            hit->solved = false;
+            *out = hit;
+            return 0;
+        }
+    }
+    DAQPBatch *b = new DAQPBatch();
+    b->device = device;
+    b->env_key = T.env_key;
+    b->recheck = !T.on(SW_NO_RECHECK);
+    if (hipSetDevice(device) != hipSuccess) { set_err("hipSetDevice(%d) failed", device); delete b; return DAQP_EXIT_UNSUPPORTED; }
+    if (!plan_shape(N, n, m, ms, ns_max, group, T, &b->plan, why)) { set_err("%s", why); delete b; return DAQP_EXIT_UNSUPPORTED; }
+    if (b->plan.wg_W > 0) plan_on_device(b, T);
+    BatchDev &d = b->d;
+    plan_fill(b->plan, &d);
+    if (settings) d.st = *settings; else default_settings(&d.st);
+    {   // period of the constant device clock behind s_memrealtime (settings->time_limit): asked of the runtime, not assumed
+        int khz = 0;
+        d.tick_s = (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) ? 1.0 / (1e3 * (double)khz) : 1e-8;
+        d.tstart = nullptr;
+    }
+    int rc = allocate(b);
     if (!rc && hipMemcpy(b->st_dev, &d.st, sizeof(DAQPSettings), hipMemcpyHostToDevice) != hipSuccess) rc = 1;
     d.st_dev = b->st_dev;
     if (rc) { daqp_batch_free(b); return DAQP_EXIT_UNSUPPORTED; }
     // padding rows/columns of the blocked M image are never written by the kernels: keep them defined
-    if (hipMemset(d.Mblk, 0, Nf * d.nblk * d.npair * 128 * sizeof(double)) != hipSuccess ||
-        hipMemset(d.vecs, 0, Nn * 5 * cap * sizeof(double)) != hipSuccess ||
-        hipMemset(d.qs, 0, Nn * sizeof(QState)) != hipSuccess) {
+    if (hipMemset(d.Mblk, 0, (size_t)b->plan.factor_sets * d.nblk * d.npair * 128 * sizeof(double)) != hipSuccess ||
+        hipMemset(d.vecs, 0, (size_t)N * 5 * d.cap * sizeof(double)) != hipSuccess ||
+        hipMemset(d.qs, 0, (size_t)N * sizeof(QState)) != hipSuccess) {
         set_err("hipMemset failed");
         daqp_batch_free(b);
         return DAQP_EXIT_UNSUPPORTED;
@@ -1119,6 +932,29 @@ static int batch_create(DAQPBatch **out, int N, int n, int m, int ms, int ns_max
     for (auto &e : b->ev) if (hipEventCreate(&e) != hipSuccess) { set_err("hipEventCreate failed"); daqp_batch_free(b); return DAQP_EXIT_UNSUPPORTED; }
     *out = b;
     return 0;
+}
+
+// The plan of a shape under the current environment and the given device numbers (plan.hip.h), as one line of key=value in a fixed order;
+// a shape the library refuses gives refused=<text>.  Needs no device.  Returns what snprintf would.
+int daqp_amd_describe_plan(int N, int n, int m, int ms, int ns_max, int cus, int per_cu, int tier_attr_ok, int per_cu_tier, char *buf, int len)
+{
+    const Tuning T = read_tuning();
+    SolvePlan p;
+    char why[kPlanWhy];
+    if (!plan_shape(N, n, m, ms, ns_max, 0, T, &p, why)) return snprintf(buf, (size_t)(len > 0 ? len : 0), "refused=%s", why);
+    plan_device(&p, T, cus, per_cu, tier_attr_ok != 0, per_cu_tier);
+    char line[2048];
+    describe_plan(p, line, (int)sizeof(line));
+    return snprintf(buf, (size_t)(len > 0 ? len : 0), "%s env_key=%s", line, T.env_key.c_str());
+}
+// the same line for a live batch, followed by the device numbers it was created with (0: not asked -- only the workgroup kernel's shapes ask)
+int daqp_batch_describe(const DAQPBatch *b, char *buf, int len)
+{
+    if (!b) return -1;
+    char line[2048];
+    describe_plan(b->plan, line, (int)sizeof(line));
+    return snprintf(buf, (size_t)(len > 0 ? len : 0), "%s env_key=%s cus=%d per_cu=%d tier_attr_ok=%d per_cu_tier=%d", line, b->env_key.c_str(),
+                    b->dev_cus, b->dev_per_cu, b->dev_tier_attr_ok, b->dev_per_cu_tier);
 }
 
 void daqp_batch_free(DAQPBatch *b)
@@ -1352,19 +1188,15 @@ int batch_setup(DAQPBatch *b, const DAQPBatchProblem *p, int init_mask, bool fre
     // reduction is not built; such problems are solved on the full LDP instead (what setup_daqp + daqp_solve do): same exit
     // flag and active set, x and lam equal to ~1e-13, only the iteration count may differ (tests/test_gpu_reference_cases.py).
     const int mask = (init_mask & ~DAQP_UPDATE_eliminate) | DAQP_UPDATE_Rinv | DAQP_UPDATE_M | DAQP_UPDATE_v | DAQP_UPDATE_d | DAQP_UPDATE_sense;
-    setup_kernel_t ks = b->setup_spill ? (d.n > 256 ? k_setup<true, 8> : k_setup<true>) : k_setup<false>;
-    size_t lds_setup = b->lds_setup;
-    if (b->fast_setup) {
-        ks = pick_setup_fast(d.n, d.exact_setup == 0);
-        lds_setup = (size_t)fast_lds(d.n, d.m, d.exact_setup, d.mA).total_bytes;   // the MFMA path overlays the A tile on R^-1
-    }
+    size_t lds_setup = 0;
+    setup_kernel_t ks = pick_setup(b, d, false, false, &lds_setup);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_setup));
     if (!b->quiet_setup) HIPCHK(hipEventRecord(b->ev[0], b->stream));
     b->inputs_adopted = p->memory == DAQP_MEM_DEVICE;
-    if (!lp && b->tiny_setup) {     // sixteen problems per wavefront; singular Hessians leave flagged for the regularising re-run below
+    if (!lp && b->plan.tiny_setup) {     // sixteen problems per wavefront; singular Hessians leave flagged for the regularising re-run below
         hipLaunchKernelGGL(k_setup_tiny<4>, dim3((d.N + 15) / 16), dim3(64), 0, b->stream, d, mask);
         HIPCHK(hipGetLastError());
-    } else if (!lp && b->fast_setup && (d.ms == 0 || !getenv("DAQP_AMD_NO_BLK_BOUNDS")) && d.n > 16 && d.exact_setup == 0 && blk_setup_enabled()) {
+    } else if (!lp && b->plan.fast_setup && (d.ms == 0 || !getenv("DAQP_AMD_NO_BLK_BOUNDS")) && d.n > 16 && d.exact_setup == 0 && blk_setup_enabled()) {
         // the factorisation on the matrix cores (setup_blk.hip.h); what it does not call clearly regular it marks, and the ordered
         // kernel right behind it takes exactly those problems (every other wave of that launch leaves at its first scalar load)
         const int NT = (d.n + 15) / 16;
@@ -1385,10 +1217,9 @@ int batch_setup(DAQPBatch *b, const DAQPBatchProblem *p, int init_mask, bool fre
         // descriptor: the batch's own never carries it, whichever way this function is left (a later shared setup copies b->d)
         BatchDev l = d;
         l.defer_m = defers_m(b, d) ? 1 : 0;
-        const bool gs_now = b->setup_spill || (b->fact_gs && l.defer_m && b->fact_buf && d.setup_g && !(d.st.eps_prox > 0.0));
+        const bool gs_now = b->plan.setup_spill || (b->plan.fact_gs && l.defer_m && b->fact_buf && d.setup_g && !(d.st.eps_prox > 0.0));
         if (l.defer_m) {    // the instantiation without the general rows (k_setup_m follows): more waves per SIMD
-            ks = gs_now ? k_setup<true, 4, true> : k_setup<false, 4, true>;
-            if (gs_now && !b->setup_spill) lds_setup = (size_t)setup_lds(d.n, d.m, true).total_bytes;
+            ks = pick_setup(b, d, true, gs_now, &lds_setup);
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_setup));
         }
         // default arithmetic, factors out of LDS (the n = 200 class): Cholesky and inverse by k_fact_wg, a workgroup per problem with
@@ -1473,17 +1304,13 @@ int daqp_batch_setup_shared(DAQPBatch *b, const DAQPBatchProblem *p, int init_ma
     BatchDev t = d;
     t.N = 1; t.shared = 0; t.bu = b->wide_u; t.bl = b->wide_l; t.sense_in = nullptr;
     const int mask = DAQP_UPDATE_Rinv | DAQP_UPDATE_M | DAQP_UPDATE_v | DAQP_UPDATE_d | DAQP_UPDATE_sense;
-    setup_kernel_t ks = b->setup_spill ? (d.n > 256 ? k_setup<true, 8> : k_setup<true>) : k_setup<false>;
-    size_t lds_setup = b->lds_setup;
-    if (b->fast_setup) {
-        ks = pick_setup_fast(d.n, d.exact_setup == 0);
-        lds_setup = (size_t)fast_lds(d.n, d.m, d.exact_setup, d.mA).total_bytes;
-    }
+    size_t lds_setup = 0;
+    setup_kernel_t ks = pick_setup(b, t, false, false, &lds_setup);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_setup));
     HIPCHK(hipEventRecord(b->ev[0], b->stream));
     t.defer_m = defers_m(b, t) ? 1 : 0;
     if (t.defer_m) {
-        ks = b->setup_spill ? k_setup<true, 4, true> : k_setup<false, 4, true>;
+        ks = pick_setup(b, t, true, b->plan.setup_spill, &lds_setup);
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_setup));
     }
     hipLaunchKernelGGL(ks, dim3(1), dim3(64), lds_setup, b->stream, t, mask);
@@ -1510,10 +1337,10 @@ int daqp_batch_setup_shared(DAQPBatch *b, const DAQPBatchProblem *p, int init_ma
     }
     b->is_setup = true;
     const int upd = DAQP_UPDATE_v | DAQP_UPDATE_d;
-    const bool lazy = b->NB > 0 && !b->reg_handover && !getenv("DAQP_AMD_EAGER_UPDATE") && p->sense == nullptr;
+    const bool lazy = b->plan.NB > 0 && !b->plan.reg_handover && !getenv("DAQP_AMD_EAGER_UPDATE") && p->sense == nullptr;
     if (lazy) b->pending_mask = upd;
     else {   // a given working set is activated now, and activation needs d
-        hipLaunchKernelGGL(k_update, dim3(d.N), dim3(64), b->lds_update, b->stream, d, upd);
+        hipLaunchKernelGGL(k_update, dim3(d.N), dim3(64), b->plan.lds_update, b->stream, d, upd);
         HIPCHK(hipGetLastError());
         rc = launch_ldp(b, 1);
         if (rc) return rc;
@@ -1551,7 +1378,7 @@ static int partial_update(DAQPBatch *b, int mask, const DAQPBatchProblem *p)
     if (mask & DAQP_UPDATE_sense) { rc |= stage(b, p->sense, p->memory, N * d.m, &b->ssense, &b->nsense, &itmp); d.sense_in = itmp; }
     if (rc) return DAQP_EXIT_UNSUPPORTED;
     const setup_kernel_t ks = pick_setup_part(b);
-    const size_t lds = (size_t)setup_lds(d.n, d.m, b->setup_spill).total_bytes;
+    const size_t lds = (size_t)setup_lds(d.n, d.m, b->plan.setup_spill).total_bytes;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     BatchDev l = d;                    // (per-launch state stays off the batch's own descriptor)
     l.exact_setup = 1; l.defer_m = 0; l.fact = nullptr; l.prox_pass = 0;
@@ -1613,7 +1440,7 @@ int daqp_batch_update(DAQPBatch *b, int mask, const DAQPBatchProblem *p)
     // arrays are copied into the batch's own buffers (stream-ordered, a few tens of microseconds) instead of adopted.
     // A new sense is taken over right away, and what comes with it in the same call as well (utils.c:84-98: the bound check reads
     // the new sense, the activation at the end the new d).
-    const bool lazy = b->NB > 0 && !b->reg_handover && !getenv("DAQP_AMD_EAGER_UPDATE") && !with_sense;
+    const bool lazy = b->plan.NB > 0 && !b->plan.reg_handover && !getenv("DAQP_AMD_EAGER_UPDATE") && !with_sense;
     const int mem = p->memory;
     auto take = [&](const double *src, size_t count, double **slot, size_t *cap, const double **out) -> int {
         if (!lazy || mem != DAQP_MEM_DEVICE) return stage(b, src, mem, count, slot, cap, out);
@@ -1643,7 +1470,7 @@ int daqp_batch_update(DAQPBatch *b, int mask, const DAQPBatchProblem *p)
         HIPCHK(hipGetLastError());
     }
     if (mask & (DAQP_UPDATE_v | DAQP_UPDATE_d)) {
-        hipLaunchKernelGGL(k_update, dim3(d.N), dim3(64), b->lds_update, b->stream, d, mask & (DAQP_UPDATE_v | DAQP_UPDATE_d));
+        hipLaunchKernelGGL(k_update, dim3(d.N), dim3(64), b->plan.lds_update, b->stream, d, mask & (DAQP_UPDATE_v | DAQP_UPDATE_d));
         HIPCHK(hipGetLastError());
     }
     rc = launch_ldp(b, 1);
@@ -2054,7 +1881,7 @@ static bool update_one_deferred(DAQPWorkspace *work, DAQPBatch *b, int m, const 
 {
     const BatchDev &dd = b->d;
     if ((m & ~(DAQP_UPDATE_v | DAQP_UPDATE_d)) || !(m & (DAQP_UPDATE_v | DAQP_UPDATE_d))) return false;
-    if (dd.N != 1 || b->NB == 0 || b->reg_handover || !b->is_setup || b->reg_pending || b->was_shared || !work->sense || getenv("DAQP_AMD_EAGER_UPDATE")) return false;
+    if (dd.N != 1 || b->plan.NB == 0 || b->plan.reg_handover || !b->is_setup || b->reg_pending || b->was_shared || !work->sense || getenv("DAQP_AMD_EAGER_UPDATE")) return false;
     if (!qp->bupper || !qp->blower || ((m & DAQP_UPDATE_v) && !qp->f)) return false;
     const int n = dd.n, mm = dd.m;
     for (int i = 0; i < mm; ++i) {      // utils.c:546-567 on the mirror of the workspace's sense

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "batch_dev.hip.h"
+#include "plan.hip.h"
 
 #define DAQP_INTERNAL __attribute__((visibility("hidden")))
 namespace daqp_amd {
@@ -47,36 +48,13 @@ struct DAQPBatch {
     int *oflag = nullptr, *oiter = nullptr;
     DAQPSettings *st_dev = nullptr;
     daqp_amd::BatchDev *d_dev = nullptr;
-    int C = 1;
-    bool spill = false;
-    int NB = 0, NP = 0;   // register-resident M variant (0: stream M from HBM)
-    bool tiny_setup = false;   // n <= 12, m <= 48: the 16-problems-per-wave setup kernel (tiny_setup.hip.h)
-    bool fast_setup = false, setup_spill = false;
-    bool fact_gs = false;           // 64 < n, factors that WOULD fit the LDS of k_setup: the default arithmetic's full setup still takes k_fact_wg + the scratch variant
+    daqp_amd::SolvePlan plan;   // how this shape is solved (plan.hip.h): written by batch_create, read by everything else
     double *fact_buf = nullptr;     // [N][4] records of k_fact_wg (setup_fact.hip.h), allocated for the shapes it serves
-    // workgroup-per-problem solve kernel (wg_kernel.hip.h): shapes without a register variant and more than 64 working-set rows
     bool in_prox_loop = false;      // launches of the proximal outer loop (solve_with_prox)
-    bool use_wg = false;
-    int wg_W = 0, wg_C = 0, wg_grid = 0;
-    int wg_tier_grid = 0; size_t lds_wg_tier = 0;   // tiered launch of the workgroup kernel in front of a cold solve (0: none)
-    bool reg_handover = false;   // k_ldp_reg<2,32,*> may flag problems (more working-set rows than lanes: n = 64) for k_ldp right behind it
-    size_t lds_fb = 0;           // ... and that launch's LDS
-    bool img32 = false;          // default arithmetic: the solve launch is k_ldp_reg<NB, NP, true, 1> -- an fp32 image of M in the registers, two waves per
-                                 // SIMD, at most d.img_rows working-set rows -- with k_ldp_reg<NB, NP, true, 0> right behind it for the problems it flags
-    size_t lds_img = 0;          // ... and the image kernel's LDS
-    int img_kind = 0;            // its IMG template argument (2: the last row block split over two lanes per row; 1: full blocks)
-    // the carve-up of a WARM launch (daqp_update_ldp(UPDATE_v|UPDATE_d) fused into the solve: an MPC step starts from ~20 rows and moves a few): fewer
-    // rows held at all, so that at the same eight workgroups per CU more of them sit in LDS (the launch argument carries rows | cache, see k_ldp_reg)
-    int img_rows_warm = 0, img_cache_warm = 0;
-    size_t lds_img_warm = 0;
     // hand-overs of the last solve launch, counted on the device and copied to pinned memory without waiting: when most of a batch goes to the
     // full-register kernel anyway (working sets beyond what the image kernel holds), the next launches go there directly; every 16th tries again
     int *img_ho_pin = nullptr;
     unsigned img_skipped = 0;
-    bool img_only = false;       // no register shape holds M, but its fp32 image fits (k_ldp_reg<NB,NP,true,1> of kImgOnlyShapes, one wave per SIMD): default-mode solves run it in front of k_ldp
-    int io_nb = 0, io_np = 0;
-    int img_min_warm = 16384;
-    size_t lds_wg = 0;
     double *wide_u = nullptr, *wide_l = nullptr;   // daqp_batch_setup_shared: +-1e30 bounds of the one factorisation
     int *structural = nullptr, *shared_flag = nullptr;
     bool exact_sticky = false;   // the sense of some working-set rows was replaced without the working set being rebuilt (a sense update without a
@@ -85,7 +63,6 @@ struct DAQPBatch {
                                  // intermediate results assume the flags they were formed with) -- solves use the exact kernels until the next update
     int part_mask = 0;      // the last (re-)setup was a partial daqp_batch_update with this mask (k_setup<..., PART>): its regularising re-runs use the same kernel
     int pending_mask = 0;   // daqp_batch_update(UPDATE_v|UPDATE_d) not yet applied: the next solve launch does it (k_ldp_reg mode 2)
-    size_t lds_setup = 0, lds_ldp = 0, lds_update = 0;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed_setup = false, timed_solve = false;
     bool is_setup = false;
@@ -126,7 +103,7 @@ struct DAQPBatch {
     bool mirror_ldp_due = false;   // a deferred update's v / d have not reached the host mirrors yet: the next solve's gather brings them
     hipEvent_t ev_in = nullptr;     // the last packed host->device copy (the pinned slab is free again once it has run)
     std::string env_key;
-    int ns_max = 0;
+    int dev_cus = 0, dev_per_cu = 0, dev_tier_attr_ok = 0, dev_per_cu_tier = 0;   // what batch_create asked of the device for the plan (0: not asked)
     unsigned long long *tstart = nullptr;   // [N] start stamps of the current daqp_batch_solve (allocated when a time limit is first armed)
     std::vector<double> one_lam;
     double one_fval = 0, one_soft = 0;

@@ -3,6 +3,7 @@
 // launches and the three helpers below; the kernels are in backward_kernel.hip, refine_kernel.hip and certify_kernel.hip.
 #include <cstring>
 
+#define DAQP_AMD_PLAN_TYPES_ONLY   // (this unit reads plans; the planner's kernel headers belong to daqp_amd.hip)
 #include "host.hip.h"
 #include "backward.hip.h"
 #include "nullspace.hip.h"
@@ -159,8 +160,8 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
     }
     HIPCHK(hipSetDevice(b->device));
     const BatchDev &d = b->d;
-    const size_t N = d.N, n = d.n, m = d.m, ns = b->ns_max;
-    const bool soft = b->ns_max > 0;
+    const size_t N = d.N, n = d.n, m = d.m, ns = b->plan.ns_max;
+    const bool soft = b->plan.ns_max > 0;
     if (!soft) qsoft = nullptr, usoft = nullptr, usoft_id = nullptr;      // (ns_max == 0: usoft / usoft_id are empty, qsoft is zeroed by the entry)
     const Tier t = pick_tier(d.n, d.cap, backward_lds_bytes);
     if (!t.fits && nsw != 1) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
@@ -210,7 +211,7 @@ int refine_launch(const char *who, DAQPBatch *b, c_float *x, c_float *lam, c_flo
                   int max_steps, int memory, int nsw = -1)
 {
     if (!b || !x || !lam || !status) { set_err("%s: null batch, x, lam or status", who); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("%s: batches created with ns_max > 0 (soft constraints) are not supported: soft rows change the (2,2) block of the system", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->plan.ns_max > 0) { set_err("%s: batches created with ns_max > 0 (soft constraints) are not supported: soft rows change the (2,2) block of the system", who); return DAQP_EXIT_UNSUPPORTED; }
     if (max_steps < 1 || max_steps > kRefineMaxSteps) { set_err("%s: max_steps must be in 1..%d (got %d)", who, kRefineMaxSteps, max_steps); return DAQP_EXIT_UNSUPPORTED; }
     if (memory != DAQP_MEM_HOST && memory != DAQP_MEM_DEVICE) { set_err("%s: memory must be DAQP_MEM_HOST or DAQP_MEM_DEVICE", who); return DAQP_EXIT_UNSUPPORTED; }
     if (nsw == 1 && b->d.n > 64) { set_err("%s: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", who, b->d.n); return DAQP_EXIT_UNSUPPORTED; }
@@ -553,7 +554,7 @@ int daqp_batch_eliminate_backward(DAQPBatchElimination *el, DAQPBatch *reduced, 
     }
     if (reduced->device != el->device) { set_err("%s: the reduced batch is on device %d, the handle on device %d", who, reduced->device, el->device); return DAQP_EXIT_UNSUPPORTED; }
     if (reduced->stream != el->stream) { set_err("%s: the reduced batch and the handle are on different streams: the three launches are ordered by sharing one", who); return DAQP_EXIT_UNSUPPORTED; }
-    if (reduced->ns_max > 0) { set_err("%s: reduced batches created with ns_max > 0 (soft constraints) are not supported: a SOFT kept row is weighted by the reduced q_k", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (reduced->plan.ns_max > 0) { set_err("%s: reduced batches created with ns_max > 0 (soft constraints) are not supported: a SOFT kept row is weighted by the reduced q_k", who); return DAQP_EXIT_UNSUPPORTED; }
     if (which == 1 && d.nr > 64) { set_err("%s: which == 1 needs nr <= 64 (nr = %d): the null-space kernel holds a problem in one wavefront", who, d.nr); return DAQP_EXIT_UNSUPPORTED; }
     if (!reduced->is_setup || !reduced->solved || reduced->pending_mask) {
         set_err("%s: the last operation on the reduced batch was not a successful daqp_batch_solve", who);
@@ -602,7 +603,7 @@ void daqp_batch_elimination_free(DAQPBatchElimination *el)
 int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int memory)
 {
     if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported: daqp_batch_backward_soft"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->plan.ns_max > 0) { set_err("daqp_batch_backward: batches created with ns_max > 0 (soft constraints) are not supported: daqp_batch_backward_soft"); return DAQP_EXIT_UNSUPPORTED; }
     return backward_launch("daqp_batch_backward", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory);
 }
 
@@ -611,7 +612,7 @@ int daqp_batch_backward(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_floa
 int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower, int *status, int which, int memory)
 {
     if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_nullspace: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_backward_nullspace: batches created with ns_max > 0 (soft constraints) are not supported: q_k = c_k H^-1 c_k' does not exist for a singular H"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->plan.ns_max > 0) { set_err("daqp_batch_backward_nullspace: batches created with ns_max > 0 (soft constraints) are not supported: q_k = c_k H^-1 c_k' does not exist for a singular H"); return DAQP_EXIT_UNSUPPORTED; }
     if (which != 0 && which != 1) { set_err("daqp_batch_backward_nullspace: which must be 0 (proximal problems only) or 1 (every problem)"); return DAQP_EXIT_UNSUPPORTED; }
     if (which == 1 && b->d.n > 64) { set_err("daqp_batch_backward_nullspace: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", b->d.n); return DAQP_EXIT_UNSUPPORTED; }
     if (b->is_setup && b->d.H == nullptr) { set_err("daqp_batch_backward_nullspace: the batch has no Hessian of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
@@ -625,7 +626,7 @@ int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c
 {
     if (!b || !grad_x || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_soft: null batch or array"); return DAQP_EXIT_UNSUPPORTED; }
     const int rc = backward_launch("daqp_batch_backward_soft", b, grad_x, dz, dbupper, dblower, qsoft, usoft, usoft_id, status, memory);
-    if (rc == 0 && b->ns_max == 0 && qsoft && b->d.m) {      // no SOFT instantiation ran: no row of any working set is soft
+    if (rc == 0 && b->plan.ns_max == 0 && qsoft && b->d.m) {      // no SOFT instantiation ran: no row of any working set is soft
         const size_t bytes = sizeof(double) * (size_t)b->d.N * b->d.m;
         if (memory == DAQP_MEM_DEVICE) HIPCHK(hipMemsetAsync(qsoft, 0, bytes, b->stream));
         else memset(qsoft, 0, bytes);
@@ -641,7 +642,7 @@ int daqp_batch_backward_dual(DAQPBatch *b, const c_float *grad_x, const c_float 
     if (!b || !dz || !dbupper || !dblower || !status) { set_err("daqp_batch_backward_dual: null batch or output array"); return DAQP_EXIT_UNSUPPORTED; }
     if (!grad_x && !grad_lam) { set_err("daqp_batch_backward_dual: grad_x and grad_lam are both null: there is nothing to differentiate"); return DAQP_EXIT_UNSUPPORTED; }
     if (which < -1 || which > 1) { set_err("daqp_batch_backward_dual: which must be -1 (Gram only), 0 (null space for the proximal problems) or 1 (null space for every problem)"); return DAQP_EXIT_UNSUPPORTED; }
-    if (b->ns_max > 0) { set_err("daqp_batch_backward_dual: batches created with ns_max > 0 (soft constraints) are not supported: the multiplier of a soft row is not built here"); return DAQP_EXIT_UNSUPPORTED; }
+    if (b->plan.ns_max > 0) { set_err("daqp_batch_backward_dual: batches created with ns_max > 0 (soft constraints) are not supported: the multiplier of a soft row is not built here"); return DAQP_EXIT_UNSUPPORTED; }
     if (which == 1 && b->d.n > 64) { set_err("daqp_batch_backward_dual: which == 1 needs n <= 64 (n = %d): the null-space kernel holds a problem in one wavefront", b->d.n); return DAQP_EXIT_UNSUPPORTED; }
     if (which >= 0 && b->is_setup && b->d.H == nullptr) { set_err("daqp_batch_backward_dual: the batch has no Hessian of the caller's to read"); return DAQP_EXIT_UNSUPPORTED; }
     if (!grad_lam) return which < 0 ? daqp_batch_backward(b, grad_x, dz, dbupper, dblower, status, memory)

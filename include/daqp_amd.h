@@ -726,6 +726,15 @@ int daqp_batch_read_ldp(DAQPBatch *b, int q, c_float *M, c_float *R, c_float *v,
 const char *daqp_amd_last_error(void);
 int daqp_amd_device_count(void);
 const char *daqp_amd_version(void);
+/* How a shape is solved: the library's plan (kernel family, register shape, fp32 image, workgroup kernel, setup kernel, LDS sizes, scratch
+ * buffers: csrc/plan.hip.h) as ONE line of key=value pairs in a fixed key order, written to buf (at most len bytes, always terminated); returns
+ * what snprintf would.  daqp_amd_describe_plan needs no device: it plans (N, n, m, ms, ns_max) under the current DAQP_AMD_* environment and the
+ * device numbers given -- CU count, workgroups of the workgroup kernel per CU, whether its tiered variant accepts its LDS and how many of its
+ * workgroups fit a CU (asked of the device only for shapes of the workgroup kernel; 0 otherwise) -- and a shape the library refuses gives
+ * refused=<the text of daqp_amd_last_error>.  daqp_batch_describe writes the same line for a live batch, followed by cus= per_cu= tier_attr_ok=
+ * per_cu_tier= as the batch was created with. */
+int daqp_amd_describe_plan(int N, int n, int m, int ms, int ns_max, int cus, int per_cu, int tier_attr_ok, int per_cu_tier, char *buf, int len);
+int daqp_batch_describe(const DAQPBatch *b, char *buf, int len);
 /* always 0: the 16-problems-per-wavefront solve kernel of rounds 3-4 (slower than the default one) has been removed; kept for callers that asked */
 int daqp_amd_has_tiny(void);
 
