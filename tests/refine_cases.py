@@ -33,8 +33,9 @@ CASES = [
 COND_RANGE = (1e6, 1e9)
 
 
-def make(n, m, ms, seed, fill, amp=1):
-    """dict(H, f, A, bupper, blower, x, lam, W (ids, ascending), lower (bool per row of W), n, m, ms) of one planted problem"""
+def make(n, m, ms, seed, fill, amp=1, k=None):
+    """dict(H, f, A, bupper, blower, x, lam, W (ids, ascending), lower (bool per row of W), n, m, ms) of one planted problem; k: the rows
+    of its working set (default: about n / 4)"""
     rng = np.random.default_rng([9100, n, seed])
     L = np.tril(rng.integers(-amp, amp + 1, (n, n)) * (rng.random((n, n)) < fill), -1).astype(np.float64) + np.eye(n)
     H = L @ L.T
@@ -43,7 +44,7 @@ def make(n, m, ms, seed, fill, amp=1):
     if not x.any():
         x[0] = 1.0
     # the active set: up to two simple bounds, the rest general rows, about n / 4 rows in all
-    k = max(4, n // 4)
+    k = max(4, n // 4) if k is None else k
     nb = min(ms, 2)
     W = np.sort(np.concatenate([rng.choice(ms, nb, replace=False) if nb else np.zeros(0, np.int64),
                                 ms + rng.choice(m - ms, k - nb, replace=False)])).astype(np.int64)
