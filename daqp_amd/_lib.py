@@ -73,7 +73,7 @@ EXPORTS = [
     "daqp_batch_device_bytes", "daqp_batch_rechecked", "daqp_batch_set_recheck", "daqp_batch_recheck_ms", "daqp_amd_last_error", "daqp_amd_device_count", "daqp_amd_version", "daqp_amd_has_tiny",
     "setup_daqp_ldp", "daqp_ldp", "ldp2qp_solution", "daqp_extract_result",
     "daqp_minrep_batch", "daqp_minrep_batch_info", "daqp_batch_reset", "reset_daqp_workspace", "daqp_deactivate_constraints",
-    "daqp_batch_backward", "daqp_batch_backward_soft", "daqp_batch_backward_nullspace", "daqp_batch_backward_dual", "daqp_certify_batch", "daqp_batch_refine", "daqp_batch_refine_nullspace",
+    "daqp_batch_backward", "daqp_batch_backward_soft", "daqp_batch_backward_nullspace", "daqp_batch_backward_dual", "daqp_batch_backward_soft_dual", "daqp_certify_batch", "daqp_batch_refine", "daqp_batch_refine_nullspace",
     "daqp_batch_eliminate", "daqp_batch_eliminate_update", "daqp_batch_elimination_problem", "daqp_batch_elimination_flags", "daqp_batch_expand",
     "daqp_batch_elimination_basis", "daqp_batch_elimination_read", "daqp_batch_elimination_bytes", "daqp_batch_elimination_free",
     "daqp_batch_eliminate_backward",
@@ -319,6 +319,7 @@ def lib():
     L.daqp_batch_backward_soft.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
     L.daqp_batch_backward_nullspace.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci]
     L.daqp_batch_backward_dual.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
+    L.daqp_batch_backward_soft_dual.argtypes = [vp] * 12 + [ci]
     L.daqp_certify_batch.argtypes = [C.POINTER(DAQPBatchCertificate), C.POINTER(DAQPBatchProblem), vp, vp, ci, ci, vp]
     L.daqp_batch_refine.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci]
     L.daqp_batch_refine_nullspace.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci]

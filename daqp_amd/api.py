@@ -334,8 +334,8 @@ class BatchModel:
 
         grad_lam (N, m) = dl/dlam with respect to the signed multipliers of the solve: daqp_batch_backward_dual -- the same system
         with grad_lam on the working set in the second block of its right-hand side, the same outputs and the same formulas.
-        grad_x may then be None (= 0).  nullspace selects its `which` (False: -1, True: 0, "all": 1); ns_max == 0 only.  Without
-        grad_lam the calls above are made, unchanged."""
+        grad_x may then be None (= 0).  nullspace selects its `which` (False: -1, True: 0, "all": 1); ns_max == 0 only (a model with soft
+        rows: backward_soft below).  Without grad_lam the calls above are made, unchanged."""
         N, n, m, ns = self.N, self.n, self.m, self.ns
         if nullspace not in (False, True, "all"):
             raise ValueError('nullspace must be False, True or "all"')
@@ -399,6 +399,40 @@ class BatchModel:
         if rc != 0:
             raise RuntimeError(f"daqp_batch_backward_dual failed ({rc}): {_lib.last_error()}")
         self._bw_keep = [[g, gl], o]      # the launch reads / writes them after this call has returned
+        return o
+
+    def backward_soft(self, grad_x=None, grad_lam=None, grad_slack=None, lam=None, out="torch"):
+        """The adjoint of the last solve of a model with soft rows for a loss l(x, lam, fval, soft_slack)
+        (daqp_batch_backward_soft_dual, include/daqp_amd.h): grad_x (N, n) = dl/dx, grad_lam (N, m) = dl/dlam, grad_slack (N,) =
+        dl/dsoft_slack, each None for zero, not all three; lam (N, m): the multipliers solve() returned, needed with grad_slack.
+        ONE system, K [dz; dnu] = [grad_x; ghat_lam on W] with -S in the (2,2) block of K and ghat_lam_k = grad_lam_k + 2 grad_slack
+        rho_soft q_k lam_k on the SOFT rows of the working set.  Returns the dict of backward() on a soft model -- dz, dbupper,
+        dblower, status, qsoft, usoft, usoft_id -- for the same formulas; the q_k-dependence terms take dsig_k = dnu_k lam_k +
+        grad_slack lam_k^2 - 1/2 grad_fval lam_k^2 (daqp_amd.layer.soft_gradient_terms, dsig_extra).  Without grad_lam and grad_slack
+        the result is that of backward(grad_x), bit for bit.  out='torch': device tensors in and out, nothing waits; out='numpy': host
+        arrays."""
+        N, n, m, ns = self.N, self.n, self.m, self.ns
+        if out == "torch":
+            dev = torch.device("cuda", self.device)
+            conv = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
+            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+            ptr = lambda a: None if a is None else a.data_ptr()
+            f64, i32, mem = torch.float64, torch.int32, MEM_DEVICE
+        else:
+            conv = lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64)
+            new = lambda shape, dtype: np.empty(shape, dtype)
+            ptr = lambda a: None if a is None else a.ctypes.data
+            f64, i32, mem = np.float64, np.int32, MEM_HOST
+        ins = [conv(grad_x), conv(grad_lam), conv(grad_slack), conv(lam)]
+        for name, a, shape in zip(("grad_x", "grad_lam", "grad_slack", "lam"), ins, ((N, n), (N, m), (N,), (N, m))):
+            if a is not None and tuple(a.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}")
+        o = dict(dz=new((N, n), f64), dbupper=new((N, m), f64), dblower=new((N, m), f64), status=new((N,), i32),
+                 qsoft=new((N, m), f64), usoft=new((N, ns, n), f64), usoft_id=new((N, ns), i32))
+        rc = lib().daqp_batch_backward_soft_dual(self._h, *[ptr(a) for a in ins], *[ptr(o[k]) for k in self._BW_KEYS], ptr(o["status"]), mem)
+        if rc != 0:
+            raise RuntimeError(f"daqp_batch_backward_soft_dual failed ({rc}): {_lib.last_error()}")
+        self._bw_keep = [ins, o]      # the launch reads / writes them after this call has returned
         return o
 
     def certify(self, res, out=None):

@@ -36,6 +36,14 @@
 // units and meets the unit-length scaling alone: rhs_k = (N_k w - g_lamW_k) / |N_k|.  grad_x may be null (= 0) there.  With W empty
 // grad_lam is not read.  DUAL == false compiles to what the kernel was before.
 //
+// Both (SOFT && DUAL: daqp_batch_backward_soft_dual).  A loss that also depends on soft_slack = sum_k S_k lam_k^2 (the SOFT rows of W)
+// adds its derivative through lam to the second block, with g_s = grad_slack[q] and lam the multipliers of the solve:
+//     ghat_lamW[k] = grad_lam[WS[k]] + 2 g_s rho_soft q_k lam_k  on the SOFT rows of W,  grad_lam[WS[k]] elsewhere
+//     (N_W N_W' + S) dnu = N_W w - ghat_lamW
+// formed where q_k = G_kk is read and kept in y[] (idle until the triangular solves), so the LDS carve-up is that of SOFT alone --
+// and that of DUAL alone: gp[] is the buffer every instantiation has.  grad_lam and grad_slack may each be null (= 0).  The part of
+// dl/dS_k that does not go through lam (g_s lam_k^2, and the envelope term of fval) is the caller's (include/daqp_amd.h).
+//
 // Mapping: one workgroup per problem; T = 64 (ONE wavefront, R^-1, the rows and the Gram matrix in LDS) while n <= 64 and all of it
 // fits (with ns_max = 0 the working set holds at most 65 rows and it always does) -- and T = 256 beyond, R^-1 streamed from HBM, rows and Gram matrix in LDS where they fit (NL) and
 // in a per-WORKGROUP scratch in HBM where they do not (persistent workgroups, problem q, q + grid, ...).  All arithmetic is fp64.
@@ -53,6 +61,8 @@ struct BackwardArgs {
     double *qsoft, *usoft;        // [N][m], [N][ns_max][n]: SOFT kernels only, each may be null
     int *usoft_id;                // [N][ns_max], may be null
     const double *grad_lam;       // [N][m]: DUAL kernels only (read on W); grad_x may be null there (= 0)
+    const double *grad_slack;     // [N]: SOFT && DUAL kernels only, may be null (= 0); grad_lam may be null there as well (= 0)
+    const double *lam;            // [N][m]: the signed multipliers of the solve (read on the SOFT rows of W), null iff grad_slack is
 };
 
 // LDS of one workgroup in bytes: w, g', rs (n each), rhs, y, sn, dg (cap each), then R^-1 (RL), rows + Gram (NL), ids, side, flag
@@ -168,6 +178,11 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
                     const double d = G[tri(k) + k];
                     if (!(d > 0.0)) { sn[k] = 0.0; *bad = 1; } else sn[k] = 1.0 / sqrt(d);
                     if constexpr (SOFT) { if ((side[k] & 2) && a.qsoft) a.qsoft[(size_t)q * m + ids[k]] = d; }      // q_k = |N_k|^2
+                    if constexpr (SOFT && DUAL) {      // ghat_lamW (in y, free until the solve): q_k is in hand here
+                        double gh = a.grad_lam ? a.grad_lam[(size_t)q * m + ids[k]] : 0.0;
+                        if ((side[k] & 2) && a.grad_slack) gh += 2.0 * a.grad_slack[q] * b.st.rho_soft * d * a.lam[(size_t)q * m + ids[k]];
+                        y[k] = gh;
+                    }
                 }
                 __syncthreads();
                 if (*bad) st = DAQP_BACKWARD_SINGULAR;
@@ -182,7 +197,9 @@ __global__ __launch_bounds__(T) void k_backward(BatchDev b, BackwardArgs a)
                         if (l <= k) G[tri(k) + l] *= sn[k] * sn[l];
                     }
                 }
-                if constexpr (DUAL) {      // N_W w - g_lamW: the rows above are unscaled already, so sn is all that meets g_lam
+                if constexpr (SOFT && DUAL) {      // N_W w - ghat_lamW
+                    for (int k = tid; k < na; k += T) rhs[k] = (rhs[k] - y[k]) * sn[k];
+                } else if constexpr (DUAL) {      // N_W w - g_lamW: the rows above are unscaled already, so sn is all that meets g_lam
                     const double *gl = a.grad_lam + (size_t)q * m;
                     for (int k = tid; k < na; k += T) rhs[k] = (rhs[k] - gl[ids[k]]) * sn[k];
                 } else {

@@ -15,6 +15,10 @@ template __global__ void k_backward<256, false, false, true>(BatchDev, BackwardA
 template __global__ void k_backward<64, true, true, false, true>(BatchDev, BackwardArgs);
 template __global__ void k_backward<256, false, true, false, true>(BatchDev, BackwardArgs);
 template __global__ void k_backward<256, false, false, false, true>(BatchDev, BackwardArgs);
+// both (daqp_batch_backward_soft_dual): g_lam and the soft_slack term on W in the second block, -S in the (2,2) block
+template __global__ void k_backward<64, true, true, true, true>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, true, true, true>(BatchDev, BackwardArgs);
+template __global__ void k_backward<256, false, false, true, true>(BatchDev, BackwardArgs);
 // the null-space adjoint: the caller's H instead of the kept factor (singular H, LPs)
 template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
 template __global__ void k_backward_nullspace<64, true>(BatchDev, NullspaceArgs);

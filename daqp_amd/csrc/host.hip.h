@@ -27,7 +27,7 @@ DAQP_INTERNAL extern std::atomic<unsigned long long> g_devices_used;   // bit pe
 // what one family of post-solve calls (post_solve.hip) keeps on the batch: one each, so that a call of one leaves the other's as it is
 struct PostSolveBufs {
     double *scratch = nullptr; int grid = 0;   // [grid][the kernel's *_scratch_doubles]: rows and Gram matrix of shapes that LDS does not hold
-    void *slot[9] = {};         // device copies of host-resident arguments, in the order the entry stages them (each allocated when first needed)
+    void *slot[11] = {};        // device copies of host-resident arguments, in the order the entry stages them (each allocated when first needed)
 };
 } // namespace daqp_amd
 

@@ -24,6 +24,9 @@ extern template __global__ void k_backward<256, false, false, true>(BatchDev, Ba
 extern template __global__ void k_backward<64, true, true, false, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, true, false, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward<256, false, false, false, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<64, true, true, true, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, true, true, true>(BatchDev, BackwardArgs);
+extern template __global__ void k_backward<256, false, false, true, true>(BatchDev, BackwardArgs);
 extern template __global__ void k_backward_nullspace<64>(BatchDev, NullspaceArgs);
 extern template __global__ void k_backward_nullspace<64, true>(BatchDev, NullspaceArgs);
 // the elimination kernels: eliminate_kernel.hip
@@ -151,8 +154,12 @@ struct Staging {
 // for every problem.  Launched for n <= 64 only: beyond, nsw == 0 leaves k_backward's DAQP_EXIT_UNSUPPORTED and nsw == 1 was refused.
 // grad_lam != null (daqp_batch_backward_dual, ns_max == 0 only): the DUAL instantiations of both kernels -- g_lam on W in the second
 // block of the right-hand side -- with the same tiers (they need no LDS of their own: backward_lds_bytes is unchanged); grad_x may then be null.
+// soft_dual (daqp_batch_backward_soft_dual, ns_max > 0 only): the SOFT && DUAL instantiations -- grad_lam and / or grad_slack (with the
+// lam of the solve) in the second block; each of the two may be null.  Their LDS is that of the SOFT ones (ghat_lam lives in y[], which
+// the SOFT and the DUAL kernels both carry and leave idle until the triangular solves), so the tier pick is the same function of (n, cap).
 int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
-                    c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory, int nsw = -1, const c_float *grad_lam = nullptr)
+                    c_float *qsoft, c_float *usoft, int *usoft_id, int *status, int memory, int nsw = -1, const c_float *grad_lam = nullptr,
+                    bool soft_dual = false, const c_float *grad_slack = nullptr, const c_float *lam = nullptr)
 {
     if (!b->is_setup || !b->solved || b->pending_mask) {
         set_err("%s: the last operation on the batch was not a successful daqp_batch_solve", who);
@@ -166,7 +173,8 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
     const Tier t = pick_tier(d.n, d.cap, backward_lds_bytes);
     if (!t.fits && nsw != 1) { set_err("%s: n = %d with working sets of %d rows does not fit the adjoint kernel", who, d.n, d.cap); return DAQP_EXIT_UNSUPPORTED; }
     void (*kb)(BatchDev, BackwardArgs);
-    if (soft) kb = t.small ? k_backward<64, true, true, true> : (t.nl ? k_backward<256, false, true, true> : k_backward<256, false, false, true>);
+    if (soft && soft_dual) kb = t.small ? k_backward<64, true, true, true, true> : (t.nl ? k_backward<256, false, true, true, true> : k_backward<256, false, false, true, true>);
+    else if (soft) kb = t.small ? k_backward<64, true, true, true> : (t.nl ? k_backward<256, false, true, true> : k_backward<256, false, false, true>);
     else if (grad_lam) kb = t.small ? k_backward<64, true, true, false, true> : (t.nl ? k_backward<256, false, true, false, true> : k_backward<256, false, false, false, true>);
     else kb = t.small ? k_backward<64, true, true, false> : (t.nl ? k_backward<256, false, true, false> : k_backward<256, false, false, false>);
     BackwardArgs a{};
@@ -179,7 +187,8 @@ int backward_launch(const char *who, DAQPBatch *b, const c_float *grad_x, c_floa
     Staging st(b, b->adjoint.slot, b->stream, memory);
     if (st.in(&a.grad_x, 0, grad_x, N * n) || st.out(&a.dz, 1, dz, N * n) || st.out(&a.dbupper, 2, dbupper, N * m) ||
         st.out(&a.dblower, 3, dblower, N * m) || st.out(&a.qsoft, 4, qsoft, N * m) || st.out(&a.usoft, 5, usoft, N * ns * n) ||
-        st.out(&a.usoft_id, 6, usoft_id, N * ns) || st.out(&a.status, 7, status, N) || st.in(&a.grad_lam, 8, grad_lam, N * m))
+        st.out(&a.usoft_id, 6, usoft_id, N * ns) || st.out(&a.status, 7, status, N) || st.in(&a.grad_lam, 8, grad_lam, N * m) ||
+        st.in(&a.grad_slack, 9, grad_slack, N) || st.in(&a.lam, 10, lam, N * m))
         return DAQP_EXIT_UNSUPPORTED;
     if (nsw != 1) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds));
@@ -648,6 +657,32 @@ int daqp_batch_backward_dual(DAQPBatch *b, const c_float *grad_x, const c_float 
     if (!grad_lam) return which < 0 ? daqp_batch_backward(b, grad_x, dz, dbupper, dblower, status, memory)
                                     : daqp_batch_backward_nullspace(b, grad_x, dz, dbupper, dblower, status, which, memory);
     return backward_launch("daqp_batch_backward_dual", b, grad_x, dz, dbupper, dblower, nullptr, nullptr, nullptr, status, memory, which, grad_lam);
+}
+
+// The adjoint of a batch with soft rows with a dual right-hand side (include/daqp_amd.h): K [dz; dnu] = [grad_x; ghat_lam on W], K with -S
+// in its (2,2) block.  No dual gradient is daqp_batch_backward_soft itself; a batch without soft rows has no S and no soft_slack, so
+// grad_slack meets no row there and the call is daqp_batch_backward_dual(which = -1), kernels and all, then the zeroed qsoft.
+int daqp_batch_backward_soft_dual(DAQPBatch *b, const c_float *grad_x, const c_float *grad_lam, const c_float *grad_slack, const c_float *lam,
+                                  c_float *dz, c_float *dbupper, c_float *dblower, c_float *qsoft, c_float *usoft, int *usoft_id,
+                                  int *status, int memory)
+{
+    const char *who = "daqp_batch_backward_soft_dual";
+    if (!b || !dz || !dbupper || !dblower || !status) { set_err("%s: null batch or output array", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (!grad_x && !grad_lam && !grad_slack) { set_err("%s: grad_x, grad_lam and grad_slack are all null: there is nothing to differentiate", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (grad_slack && !lam) { set_err("%s: grad_slack needs lam, the multipliers of the solve (null)", who); return DAQP_EXIT_UNSUPPORTED; }
+    if (!grad_lam && !grad_slack) return daqp_batch_backward_soft(b, grad_x, dz, dbupper, dblower, qsoft, usoft, usoft_id, status, memory);
+    int rc;
+    if (b->plan.ns_max == 0) {
+        if (!grad_x && !grad_lam) { set_err("%s: grad_slack alone on a batch created with ns_max == 0: it has no soft row, there is nothing to differentiate", who); return DAQP_EXIT_UNSUPPORTED; }
+        rc = daqp_batch_backward_dual(b, grad_x, grad_lam, dz, dbupper, dblower, status, -1, memory);
+        if (rc == 0 && qsoft && b->d.m) {      // no SOFT instantiation ran: no row of any working set is soft
+            const size_t bytes = sizeof(double) * (size_t)b->d.N * b->d.m;
+            if (memory == DAQP_MEM_DEVICE) HIPCHK(hipMemsetAsync(qsoft, 0, bytes, b->stream));
+            else memset(qsoft, 0, bytes);
+        }
+        return rc;
+    }
+    return backward_launch(who, b, grad_x, dz, dbupper, dblower, qsoft, usoft, usoft_id, status, memory, -1, grad_lam, true, grad_slack, lam);
 }
 
 // Iterative refinement of (x, lam) at the stored working set (include/daqp_amd.h): refine_launch above

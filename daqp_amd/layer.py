@@ -33,7 +33,16 @@ and backward is ONE daqp_batch_eliminate_backward call: the KKT system of the fu
 factor of the equality rows and the factor of the reduced Hessian (include/daqp_amd.h).  The formulas above are unchanged.  Every
 bound gradient of an equality row -- its multiplier gradient and the -g_fval lam term -- goes to bupper; blower gets zero there.
 
-Out of scope: gradients of soft_slack, lam or fval of batches with SOFT rows, per-row soft weights, proximal problems with n > 64 or
+qp_layer(..., returns=(..., "soft_slack"), soft_returns=True) takes SOFT rows on that route and adds soft_slack (N,) = sum_k S_k lam_k^2
+to the names; fval is then 1/2 x'Hx + f'x + 1/2 soft_slack.  Backward is ONE daqp_batch_backward_soft_dual launch: -S in the (2,2)
+block and ghat_lam_k = g_lam_k + 2 g_slack rho_soft q_k lam_k (SOFT rows of W) in the second block of the right-hand side.  The
+formulas are unchanged; the q_k-dependence terms take the wider
+
+    dsig_k = dnu_k lam_k - 1/2 g_fval lam_k^2 + g_slack lam_k^2
+
+(soft_slack depends on S_k directly; fval through the envelope theorem: dfval/dS_k = -1/2 lam_k^2).
+
+Out of scope: per-row soft weights, proximal problems with n > 64 or
 with SOFT rows, an LP with one shared A; with eq_rows: SOFT rows and one shared H / A.
 """
 import torch
@@ -44,7 +53,7 @@ from .api import INF, UPDATE_unconstrained, BatchModel, EliminatedBatchModel
 SOFT = 8      # DAQP_SOFT (include/daqp_amd.h)
 
 
-def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms):
+def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms, dsig_extra=None):
     """The terms that S = diag(rho_soft q_k), q_k = c_k H^-1 c_k', adds to the gradients of a batch with active SOFT rows, from what
     BatchModel.backward returns for it: lam (N, m) of the solve, dnu = dbupper + dblower (N, m), qsoft (N, m), usoft (N, ns, n),
     usoft_id (N, ns) (-1: unused slot).  Pure torch, any device.  Returns per problem
@@ -54,12 +63,14 @@ def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms):
                              no row of A)                                  add to -(lam_i dz + dnu_i x)'
         drho (N,)            sum_k dsig_k q_k
 
-    with dsig_k = dnu_k lam_k on the SOFT rows of W."""
+    with dsig_k = dnu_k lam_k on the SOFT rows of W.  dsig_extra (N, m), optional: added to dnu lam there -- what a loss that depends on
+    soft_slack or fval adds to dl/dS_k (g_slack lam_k^2 - 1/2 g_fval lam_k^2); read on the SOFT rows of W only."""
     N, ns, n = usoft.shape
     m = lam.shape[1]
     valid = usoft_id >= 0
     idx = usoft_id.clamp(min=0).long()
-    dsig = torch.gather(dnu * lam, 1, idx) * valid                                   # (N, ns), working-set order
+    dsig_all = dnu * lam if dsig_extra is None else dnu * lam + dsig_extra
+    dsig = torch.gather(dsig_all, 1, idx) * valid                                    # (N, ns), working-set order
     su = (rho_soft * dsig)[:, :, None] * usoft                                        # rho dsig_k u_k
     dH = -torch.einsum("qsi,qsj->qij", su, usoft)
     general = (valid & (idx >= ms))[:, :, None]
@@ -67,13 +78,13 @@ def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms):
     dA = torch.zeros((N, m - ms, n), dtype=usoft.dtype, device=usoft.device)
     if m > ms:
         dA.scatter_add_(1, row, 2.0 * su * general)
-    drho = (dnu * lam * qsoft).sum(1)                                                 # qsoft is zero off the SOFT rows of W
+    drho = (dsig_all * qsoft).sum(1)                                                  # qsoft is zero off the SOFT rows of W
     return dict(dH=dH, dA=dA, drho=drho)
 
 
 class _QPLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft, nullspace=False, returns=None):
+    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft, nullspace=False, returns=None, soft_returns=False):
         if not f.is_cuda:
             raise ValueError("qp_layer needs its inputs on the GPU")
         N, n = f.shape
@@ -116,7 +127,7 @@ class _QPLayer(torch.autograd.Function):
         ctx.rho_like = rho_soft if isinstance(rho_soft, torch.Tensor) else None
         ctx.ms, ctx.shared, ctx.strict, ctx.info = ms, shared, strict, info
         ctx.nullspace = bool(nullspace)
-        ctx.returns, ctx.exitflag = returns, r["exitflag"]
+        ctx.returns, ctx.exitflag, ctx.soft_returns = returns, r["exitflag"], bool(soft_returns)
         if info is not None:
             info["exitflag"] = r["exitflag"]
             info["lam"] = r["lam"]
@@ -130,7 +141,8 @@ class _QPLayer(torch.autograd.Function):
     def backward(ctx, *grads):
         bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
         if ctx.returns is not None:
-            return _QPLayer._backward_returns(ctx, dict(zip(ctx.returns, grads)))
+            g = dict(zip(ctx.returns, grads))
+            return _QPLayer._backward_soft_returns(ctx, g) if ctx.soft_returns else _QPLayer._backward_returns(ctx, g)
         grad_x, = grads
         with torch.cuda.device(x.device):
             o = bm.backward(grad_x.to(torch.float64).contiguous(), out="torch", nullspace=ctx.nullspace)
@@ -234,6 +246,88 @@ class _QPLayer(torch.autograd.Function):
             gH = gH.sum(0)
         return gH, gf, gA, gbu, gbl, None, None, None, None, None, None, None, None
 
+    @staticmethod
+    def _backward_soft_returns(ctx, g):
+        """backward of returns=(...) with soft_returns=True: ONE daqp_batch_backward_soft_dual launch with g_x, g_lam and g_slack, the
+        five formulas, the q_k-dependence terms with dsig_k = dnu_k lam_k + g_slack lam_k^2 - 1/2 g_fval lam_k^2, then the envelope
+        terms of g_fval.  A model without SOFT rows has soft_slack = 0: g_slack meets nothing."""
+        bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
+        c = lambda t: None if t is None else t.to(torch.float64).contiguous()
+        gx, gl, gv, gs = c(g.get("x")), c(g.get("lam")), c(g.get("fval")), c(g.get("soft_slack"))
+        soft = bm.ns > 0
+        if not soft:
+            gs = None
+        if gx is None and gl is None and gv is None and gs is None:
+            return (None,) * 14
+        o = None
+        with torch.cuda.device(x.device):
+            if soft and gx is None and gl is None and gs is None:      # g_fval alone: its dsig term still needs q_k and u_k
+                o = bm.backward_soft(torch.zeros_like(x), out="torch")
+            elif gx is not None or gl is not None or gs is not None:
+                o = bm.backward_soft(gx, gl, gs, lam if gs is not None else None, out="torch")
+        # (no launch: the envelope terms exist wherever the solve ended optimal)
+        status = o["status"] if o is not None else torch.where(ctx.exitflag == 1, torch.zeros_like(ctx.exitflag), ctx.exitflag)
+        if ctx.info is not None:
+            ctx.info["status"] = status
+        if ctx.strict:
+            badq = torch.nonzero(status).flatten()
+            if badq.numel():
+                q = int(badq[0])
+                raise RuntimeError(f"qp_layer: {badq.numel()} of {bm.N} problems have no derivative (first: problem {q}, status "
+                                   f"{int(status[q])}); strict=False gives them zero gradients")
+        need = ctx.needs_input_grad
+        gH = gf = gA = gbu = gbl = grho = None
+        add = lambda a, b: b if a is None else a + b
+        ok = status == 0      # a problem without a derivative gets zero gradients from every term
+        if gv is not None:
+            gv = gv * ok
+        if o is not None:
+            dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
+            sterm = None
+            if soft and (need[0] or need[2] or need[10]):      # the q_k-dependence of S
+                extra = None
+                if gs is not None:
+                    extra = (gs * ok)[:, None] * lam * lam
+                if gv is not None:
+                    extra = add(extra, -0.5 * gv[:, None] * lam * lam)
+                sterm = soft_gradient_terms(lam, dbu + dbl, o["qsoft"], o["usoft"], o["usoft_id"], ctx.rho, ms, dsig_extra=extra)
+            if need[0]:
+                gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
+                if sterm is not None:
+                    gH = gH + sterm["dH"]
+            if need[1]:
+                gf = -dz
+            if need[2]:
+                lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
+                gA = -(lg.t() @ dz + ng.t() @ x) if ctx.shared else -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
+                if sterm is not None:
+                    gA = gA + (sterm["dA"].sum(0) if ctx.shared else sterm["dA"])
+            if need[3]:
+                gbu = dbu
+            if need[4]:
+                gbl = dbl
+            if need[10] and sterm is not None:
+                grho = sterm["drho"].sum()
+        if gv is not None:
+            if need[0]:
+                gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
+            if need[1]:
+                gf = add(gf, gv[:, None] * x)
+            if need[2]:
+                lg = gv[:, None] * lam[:, ms:]
+                gA = add(gA, lg.t() @ x if ctx.shared else lg[:, :, None] * x[:, None, :])
+            if need[3]:
+                gbu = add(gbu, -gv[:, None] * lam.clamp(min=0.0))      # lam_i > 0: the row sits at (or, SOFT, beyond) its upper bound
+            if need[4]:
+                gbl = add(gbl, -gv[:, None] * lam.clamp(max=0.0))
+        if need[0] and ctx.shared and gH is not None and gH.dim() == 3:
+            gH = gH.sum(0)
+        if need[10]:
+            like = ctx.rho_like
+            grho = torch.zeros((), dtype=torch.float64, device=x.device) if grho is None else grho
+            grho = grho.to(device=like.device, dtype=like.dtype).reshape(like.shape)
+        return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho, None, None, None
+
 
 class _EliminatedQPLayer(torch.autograd.Function):
     """qp_layer(..., eq_rows=...): forward through an EliminatedBatchModel, backward through its adjoint"""
@@ -330,10 +424,11 @@ class _EliminatedQPLayer(torch.autograd.Function):
 
 
 RETURNS = ("x", "lam", "fval")
+SOFT_RETURNS = RETURNS + ("soft_slack",)
 
 
 def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sense=None, rho_soft=None, nullspace=False, returns="x",
-             eq_rows=None, **settings):
+             eq_rows=None, soft_returns=False, **settings):
     """x* (N, n) of  min 1/2 x'Hx + f'x  s.t.  blower <= [x[:ms]; A x] <= bupper  for N problems, differentiable.
 
     H (N, n, n), f (N, n), A (N, mA, n) or None, bupper / blower (N, m) with m = ms + mA (ms defaults to m - mA; blower None =
@@ -359,7 +454,13 @@ def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sens
     multipliers lam (N, m) (> 0 at an upper bound, < 0 at a lower one, 0 off the working set) and fval (N,) = 1/2 x'Hx + f'x.
     Backward is one daqp_batch_backward_dual launch for the gradients through x and lam; the gradient through fval is added in
     torch without a solve.  With a gradient through fval alone nothing is launched and status is 0 wherever the solve ended
-    optimal.  Not with SOFT rows.
+    optimal.  Not with SOFT rows, unless soft_returns=True.
+
+    soft_returns=True: returns takes SOFT rows, and one more name: "soft_slack" (N,) = sum_k rho_soft q_k lam_k^2 over the active SOFT
+    rows, from the solve's result; fval then is 1/2 x'Hx + f'x + 1/2 soft_slack, the optimal value of the penalised problem.  Backward
+    is ONE daqp_batch_backward_soft_dual launch (g_lam and 2 g_slack rho_soft q_k lam_k in the second block of the right-hand side),
+    the formulas above with dsig_k = dnu_k lam_k + g_slack lam_k^2 - 1/2 g_fval lam_k^2, and the envelope terms of g_fval; a rho_soft
+    tensor receives dl/drho_soft as without it.  A single name, "x" included, gives that one tensor.  Not with nullspace or eq_rows.
 
     eq_rows: a list or array of equality rows of [first ms rows of I; A] -- ONE ascending set of 1 .. n-1 indices for the whole batch,
     bupper == blower there.  Forward goes through EliminatedBatchModel (the rows eliminated on the device, the reduced batch of n - neq
@@ -371,6 +472,14 @@ def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sens
     sum, which is its gradient.  Raises ValueError for H or A of one shared plant (2-D) and for SOFT rows.  Without eq_rows the layer
     is what it was."""
     has_soft = sense is not None and bool(((torch.as_tensor(sense) & SOFT) != 0).any())
+    if soft_returns:
+        if eq_rows is not None or nullspace:
+            raise ValueError("qp_layer: soft_returns=True goes with neither eq_rows nor nullspace: SOFT rows are refused on both routes")
+        names = (returns,) if isinstance(returns, str) else tuple(returns)
+        if not names or len(set(names)) != len(names) or any(k not in SOFT_RETURNS for k in names):
+            raise ValueError(f'qp_layer: returns must be distinct names out of {SOFT_RETURNS} with soft_returns=True (got {returns!r})')
+        out = _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, False, names, True)
+        return out[0] if isinstance(returns, str) else out
     if eq_rows is not None:
         if has_soft:
             raise ValueError("qp_layer: eq_rows does not take SOFT rows: a SOFT kept row is weighted by the reduced q_k")

@@ -430,7 +430,8 @@ int daqp_batch_refine_nullspace(DAQPBatch *b, c_float *x /* N*n, in/out */, c_fl
  *   usoft_id  N*ns_max     the row ids k of those vectors; unused slots are -1
  * Preconditions, stream and memory semantics are those of daqp_batch_backward (`memory` applies to all eight arrays); ns_max > 0
  * is not a refusal here, and for ns_max == 0 dz, dbupper, dblower and status are bit for bit those of daqp_batch_backward (qsoft is
- * zero, usoft and usoft_id are empty).  Not differentiated: lam, fval, soft_slack.  Per-row soft weights do not exist here. */
+ * zero, usoft and usoft_id are empty).  Gradients through lam, fval and soft_slack: daqp_batch_backward_soft_dual below.  Per-row
+ * soft weights do not exist here. */
 int daqp_batch_backward_soft(DAQPBatch *b, const c_float *grad_x, c_float *dz, c_float *dbupper, c_float *dblower,
                              c_float *qsoft /* N*m */, c_float *usoft /* N*ns_max*n */, int *usoft_id /* N*ns_max */,
                              int *status, int memory);
@@ -496,12 +497,57 @@ int daqp_batch_backward_nullspace(DAQPBatch *b, const c_float *grad_x, c_float *
  * Returns nonzero, with the reason in the last-error string and without any device work, when both gradients are NULL, an output is
  * NULL, which is outside -1..1, which == 1 with n > 64, the last operation on the batch was not a successful daqp_batch_solve, or the
  * batch was created with ns_max > 0.
- * Not built: soft rows (ns_max > 0 is refused), soft_slack gradients, Jacobians and multi-RHS solves, n > 64 on the null-space
- * route, MultiBatchModel.  An eliminated batch (EliminatedBatchModel) has its own entry: daqp_batch_eliminate_backward. */
+ * Not built: soft rows (ns_max > 0 is refused), soft_slack gradients -- daqp_batch_backward_soft_dual below has both --,
+ * Jacobians and multi-RHS solves, n > 64 on the null-space route, MultiBatchModel.  An eliminated batch (EliminatedBatchModel) has
+ * its own entry: daqp_batch_eliminate_backward. */
 int daqp_batch_backward_dual(DAQPBatch *b, const c_float *grad_x /* N*n, may be NULL = 0 */,
                              const c_float *grad_lam /* N*m, may be NULL = 0 */,
                              c_float *dz, c_float *dbupper, c_float *dblower, int *status,
                              int which /* -1: Gram only; 0 / 1: as daqp_batch_backward_nullspace */, int memory);
+/* Both extensions at once: the adjoint of a batch WITH SOFT ROWS for a loss l(x, lam, fval, soft_slack).  The optimum solves
+ * K [x; lam_W] = [-f; b_W] with the symmetric K = [H C_W'; C_W -S], S = diag(rho_soft q_k on the SOFT rows of W, 0 elsewhere),
+ * q_k = c_k H^-1 c_k' (daqp_batch_backward_soft), and the solve reports
+ *
+ *        soft_slack = sum_k S_k lam_k^2  (SOFT rows of W)        fval = 1/2 x'Hx + f'x + 1/2 soft_slack
+ *
+ * With g_x = dl/dx (grad_x: N*n), g_lam = dl/dlam (grad_lam: N*m, read on W only), g_s = dl/dsoft_slack (grad_slack: N) and lam the
+ * signed multipliers the solve returned (lam: N*m, read on the SOFT rows of W), the call solves ONE system,
+ *
+ *        [ H    C_W' ] [ dz  ]   [ g_x       ]        ghat_lam[k] = g_lam[WS[k]] + 2 g_s rho_soft q_k lam_k   on the SOFT rows of W
+ *        [ C_W  -S   ] [ dnu ] = [ ghat_lamW ],       ghat_lam[k] = g_lam[WS[k]]                              elsewhere
+ *
+ * -- on the kept factor only the right-hand side of the Gram system changes, (C_W H^-1 C_W' + S) dnu = C_W H^-1 g_x - ghat_lamW.
+ * THE FIVE GRADIENT FORMULAS ARE UNCHANGED:  dl/df = -dz,  dl/dH = -1/2 (dz x' + x dz'),  dl/dA_i = -(lam_i dz + dnu_i x)' for the
+ * general rows i in W,  dl/dbupper = dbupper,  dl/dblower = dblower.  The terms of the q_k-dependence of S keep their form with a
+ * wider dsig, the caller's to form as for daqp_batch_backward_soft (g_f = dl/dfval):
+ *
+ *        dsig_k       = dnu_k lam_k - 1/2 g_f lam_k^2 + g_s lam_k^2        on the SOFT rows of W
+ *        dl/drho_soft = sum_k dsig_k q_k
+ *        dl/dH       -= rho_soft sum_k dsig_k u_k u_k'
+ *        dl/dA_i     += 2 rho_soft dsig_i u_i'
+ *
+ * g_s lam_k^2 is the direct dependence of soft_slack on S_k.  -1/2 g_f lam_k^2 is the envelope theorem: fval is the optimal value of
+ * the penalised problem with penalty s_k^2 / (2 rho_soft q_k), s_k = rho_soft q_k lam_k, so dfval/d(rho_soft q_k) = -1/2 lam_k^2.  The
+ * other envelope terms of g_f need no solve and are those of daqp_batch_backward_dual:  dl/df += g_f x,  dl/dH += 1/2 g_f x x',
+ * dl/dbupper_i, dl/dblower_i += -g_f lam_i (the row's side),  dl/dA_i += g_f lam_i x'.
+ *   dz, dbupper, dblower, status, qsoft, usoft, usoft_id    as daqp_batch_backward_soft; the last three may each be NULL
+ * Preconditions, stream, memory semantics (`memory` applies to all twelve arrays), status rules (DAQP_EXIT_SOFT_OPTIMAL is
+ * differentiable) and zeroed outputs on a non-zero status are those of daqp_batch_backward_soft.  grad_x, grad_lam and grad_slack may
+ * each be NULL (= 0).  With grad_lam == NULL and grad_slack == NULL the outputs are bit for bit those of daqp_batch_backward_soft; with
+ * zeros in them they compare equal to it.  A batch created with ns_max == 0 has no soft row and no soft_slack: grad_slack meets nothing
+ * there, and dz, dbupper, dblower and status are bit for bit those of daqp_batch_backward_dual(which = -1) (qsoft is zero).  The kernels
+ * are the SOFT ones with the DUAL right-hand side; they need no more LDS than either, so every shape runs on the path it ran on.
+ * Returns nonzero, with the reason in the last-error string and without any device work, when all three gradients are NULL (on a batch
+ * with ns_max == 0: grad_x and grad_lam), grad_slack is given without lam, an output other than the three soft arrays is NULL, or the
+ * last operation on the batch was not a successful daqp_batch_solve.
+ * Not built: the null-space route (q_k does not exist for a singular H), eliminated batches with SOFT rows, MultiBatchModel, per-row
+ * soft weights, Jacobians. */
+int daqp_batch_backward_soft_dual(DAQPBatch *b, const c_float *grad_x /* N*n, may be NULL */, const c_float *grad_lam /* N*m, may be NULL */,
+                                  const c_float *grad_slack /* N, may be NULL */,
+                                  const c_float *lam /* N*m, required iff grad_slack != NULL */,
+                                  c_float *dz, c_float *dbupper, c_float *dblower,
+                                  c_float *qsoft, c_float *usoft, int *usoft_id,
+                                  int *status, int memory);
 /* ---- the certificate of a batch of (x, lam) pairs: KKT residuals and Farkas measures, on the device, in twice the working precision
  * (certify.hip.h).  Stateless: no DAQPBatch, no exit flags -- it reads the caller's H, f, A, bupper, blower, sense, x and lam and nothing
  * else, so it certifies the answer of any solver and depends on no adopted pointer.  With C = [I_ms ; A] and the reference's sign

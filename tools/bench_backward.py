@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time of BatchModel.backward next to the forward step it follows, at the two headline shapes of BASELINE.md.
 
-  python tools/bench_backward.py [--configs C2,C3] [--soft | --nullspace | --dual] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
+  python tools/bench_backward.py [--configs C2,C3] [--soft | --soft-dual | --nullspace | --dual] [--batch N] [--steps K] [--warmup W] [--out profiles/NAME.jsonl]
 
 Per shape: N device-resident QPs (daqp_amd.synthetic.generate_batch_torch), forward = BatchModel.setup + solve with device outputs,
 backward = one BatchModel.backward on a device-resident grad_x; both timed with HIP events around K calls after W warm-up calls
@@ -12,7 +12,10 @@ created with ns_max = NS_SOFT: the SOFT instantiations of the adjoint kernel, wi
 kernel (daqp_batch_backward_nullspace, which = 1) -- timed next to the Gram adjoint and the forward step; the largest difference
 between the two adjoints, relative to the max norm of the Gram adjoint's [dz; dnu], goes into the record.
 --dual: on the same batch, BatchModel.backward(g, grad_lam=g_lam) -- daqp_batch_backward_dual, which = -1: the Gram adjoint with g_lam
-on the working set in the second block of its right-hand side -- timed next to the plain adjoint and the forward step."""
+on the working set in the second block of its right-hand side -- timed next to the plain adjoint and the forward step.
+--soft-dual: the batch of --soft, and BatchModel.backward_soft(g, g_lam, g_slack, lam) -- daqp_batch_backward_soft_dual: the SOFT kernels
+with g_lam and the soft_slack term in the second block -- timed next to daqp_batch_backward_soft on the same solved batch.  Only a
+right-hand side differs between the two: the pair is a record, not a rate."""
 import argparse
 import json
 import os
@@ -42,6 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C2,C3")
     ap.add_argument("--soft", action="store_true")
+    ap.add_argument("--soft-dual", action="store_true")
     ap.add_argument("--nullspace", action="store_true")
     ap.add_argument("--dual", action="store_true")
     ap.add_argument("--batch", type=int, default=0)
@@ -49,6 +53,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "backward_bench.jsonl"))
     a = ap.parse_args()
+    a.soft = a.soft or a.soft_dual
     if a.soft and (a.nullspace or a.dual):
         ap.error("--nullspace and --dual do not take soft rows")
     import torch
@@ -98,6 +103,12 @@ def main():
             dual_ms = timed(lambda: bm.backward(g, grad_lam=gl), a.steps, a.warmup)
             extra.update(dual=True, dual_ms=round(dual_ms, 4), dual_over_backward=round(dual_ms / bwd_ms, 4),
                          dual_over_forward=round(dual_ms / fwd_ms, 4), dual_status_ok=int((o3["status"] == 0).sum()))
+        if a.soft_dual:
+            gl, gs = torch.randn(N, m, dtype=torch.float64, device="cuda"), torch.randn(N, dtype=torch.float64, device="cuda")
+            o4 = bm.backward_soft(g, gl, gs, r["lam"])
+            sd_ms = timed(lambda: bm.backward_soft(g, gl, gs, r["lam"]), a.steps, a.warmup)
+            extra.update(soft_dual=True, soft_dual_ms=round(sd_ms, 4), soft_dual_over_backward=round(sd_ms / bwd_ms, 4),
+                         soft_dual_over_forward=round(sd_ms / fwd_ms, 4), soft_dual_status_ok=int((o4["status"] == 0).sum()))
         rec = dict(tool="bench_backward", config=cfg, N=N, n=n, m=m, ms=ms, n_active=nact, steps=a.steps, warmup=a.warmup,
                    forward_ms=round(fwd_ms, 4), forward_setup_kernels_ms=round(setup_ms, 4), forward_solve_kernels_ms=round(solve_ms, 4),
                    backward_ms=round(bwd_ms, 4), backward_over_forward=round(bwd_ms / fwd_ms, 4),
