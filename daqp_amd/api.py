@@ -8,6 +8,7 @@
 Everything goes through the C ABI of libdaqp_amd.so; torch tensors on the GPU are passed by
 device pointer (no copy), numpy arrays are staged by the library.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -194,6 +195,79 @@ def _ptr(a, dtype, keep):
     return arr.ctypes.data, MEM_HOST
 
 
+def _pointers(arrays):
+    """pointers and the one memory side of (name, array, dtype) triples; what must stay referenced comes back by name"""
+    keep, ptrs, mems = {}, [], set()
+    for name, a, dt in arrays:
+        tmp = []
+        p, mem = _ptr(a, dt, tmp)
+        ptrs.append(p)
+        if mem is not None:
+            mems.add(mem)
+            keep[name] = tmp[0]
+    if len(mems) > 1:
+        raise ValueError("mix of host and device arrays in one call")
+    return ptrs, (mems.pop() if mems else MEM_HOST), keep
+
+
+def _problem_pointers(H, f, A, bupper, blower, sense):
+    return _pointers((("H", H, np.float64), ("f", f, np.float64), ("A", A, np.float64), ("bupper", bupper, np.float64),
+                      ("blower", blower, np.float64), ("sense", sense, np.int32)))
+
+
+_Kit = collections.namedtuple("_Kit", "conv new ptr f64 i32 mem")
+
+
+def _kit(out, device):
+    """What a call needs to take inputs and make outputs on one side -- out='torch': tensors on `device` (a torch.device, or the index
+    of a GPU), out='numpy': host arrays: conv(a) = a as a contiguous float64 array of that side (None stays None), new(shape, dtype),
+    ptr(a) = its address (None stays None), the two dtypes f64 and i32, and the library's memory tag."""
+    if out == "torch":
+        dev = device if isinstance(device, torch.device) else torch.device("cuda", device)
+        return _Kit(lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous(),
+                    lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev),
+                    lambda a: None if a is None else a.data_ptr(), torch.float64, torch.int32, MEM_DEVICE)
+    return _Kit(lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64),
+                lambda shape, dtype: np.empty(shape, dtype),
+                lambda a: None if a is None else a.ctypes.data, np.float64, np.int32, MEM_HOST)
+
+
+_RESULT_KEYS = ("x", "lam", "fval", "soft_slack", "exitflag", "iter")
+
+
+def _result(N, n, m, out, device):
+    """(the result dict of a solve of N problems, unfilled, and the DAQPBatchResult that points into it)"""
+    k = _kit(out, device)
+    o = dict(x=k.new((N, n), k.f64), lam=k.new((N, m), k.f64), fval=k.new((N,), k.f64), soft_slack=k.new((N,), k.f64),
+             exitflag=k.new((N,), k.i32), iter=k.new((N,), k.i32))
+    return o, DAQPBatchResult(*[k.ptr(o[key]) for key in _RESULT_KEYS], k.mem, 0, 0)
+
+
+_BW_KEYS = ("dz", "dbupper", "dblower", "qsoft", "usoft", "usoft_id")
+
+
+def _adjoint(model, out, entry, handles, ins, soft=False, which=None):
+    """One adjoint call for BatchModel and EliminatedBatchModel: entry(*handles, inputs, outputs, status[, which], memory).  ins: (name,
+    array or None, shape) per input, converted to the side of `out` and checked by name; outputs dz, dbupper, dblower and status are
+    allocated, and qsoft, usoft, usoft_id with them where soft is set.  Returns the dict of outputs; the model keeps inputs and outputs
+    alive, since the launch reads / writes them after this call has returned."""
+    N, n, m, ns = model.N, model.n, model.m, model.ns
+    k = _kit(out, model.device)
+    arrays = [k.conv(a) for _, a, _ in ins]
+    for (name, _, shape), a in zip(ins, arrays):
+        if a is not None and tuple(a.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}")
+    o = dict(dz=k.new((N, n), k.f64), dbupper=k.new((N, m), k.f64), dblower=k.new((N, m), k.f64), status=k.new((N,), k.i32))
+    if soft:
+        o.update(qsoft=k.new((N, m), k.f64), usoft=k.new((N, ns, n), k.f64), usoft_id=k.new((N, ns), k.i32))
+    rc = getattr(lib(), entry)(*handles, *[k.ptr(a) for a in arrays], *[k.ptr(o[key]) for key in _BW_KEYS[:6 if soft else 3]], k.ptr(o["status"]),
+                               *(() if which is None else (which,)), k.mem)
+    if rc != 0:
+        raise RuntimeError(f"{entry} failed ({rc}): {_lib.last_error()}")
+    model._bw_keep = [arrays, o]
+    return o
+
+
 class BatchModel:
     """Device-resident workspaces of N QPs of one shape: setup -> solve -> {update(f, bounds) -> solve}*.
 
@@ -235,20 +309,7 @@ class BatchModel:
         """DAQPBatchProblem of the given arrays.  Device arrays are used in place by the library (and bounds / f are read
         again by every later update and solve), so each one stays referenced under its own name until a later call
         replaces THAT array -- an update(f=...) must not drop the bounds adopted at setup."""
-        keep = {}
-        mems = set()
-        ptrs = []
-        for name, a, dt in (("H", H, np.float64), ("f", f, np.float64), ("A", A, np.float64), ("bupper", bupper, np.float64),
-                            ("blower", blower, np.float64), ("sense", sense, np.int32)):
-            tmp = []
-            p, mem = _ptr(a, dt, tmp)
-            ptrs.append(p)
-            if mem is not None:
-                mems.add(mem)
-                keep[name] = tmp[0]
-        if len(mems) > 1:
-            raise ValueError("mix of host and device arrays in one call")
-        mem = mems.pop() if mems else MEM_HOST
+        ptrs, mem, keep = _problem_pointers(H, f, A, bupper, blower, sense)
         if mem == MEM_DEVICE:
             self._keep.update(keep)
         return DAQPBatchProblem(self.N, self.n, self.m, self.ms, *ptrs, mem), keep
@@ -292,29 +353,12 @@ class BatchModel:
 
     def solve(self, out="numpy"):
         """Returns dict(x, lam, fval, exitflag, iter, soft_slack); out='numpy' or 'torch' (device tensors)."""
-        N, n, m = self.N, self.n, self.m
-        if out == "torch":
-            dev = torch.device("cuda", self.device)
-            o = dict(x=torch.empty((N, n), dtype=torch.float64, device=dev),
-                     lam=torch.empty((N, m), dtype=torch.float64, device=dev),
-                     fval=torch.empty(N, dtype=torch.float64, device=dev),
-                     soft_slack=torch.empty(N, dtype=torch.float64, device=dev),
-                     exitflag=torch.empty(N, dtype=torch.int32, device=dev),
-                     iter=torch.empty(N, dtype=torch.int32, device=dev))
-            r = DAQPBatchResult(o["x"].data_ptr(), o["lam"].data_ptr(), o["fval"].data_ptr(), o["soft_slack"].data_ptr(),
-                                o["exitflag"].data_ptr(), o["iter"].data_ptr(), MEM_DEVICE, 0, 0)
-        else:
-            o = dict(x=np.empty((N, n)), lam=np.empty((N, m)), fval=np.empty(N), soft_slack=np.empty(N),
-                     exitflag=np.empty(N, np.int32), iter=np.empty(N, np.int32))
-            r = DAQPBatchResult(o["x"].ctypes.data, o["lam"].ctypes.data, o["fval"].ctypes.data, o["soft_slack"].ctypes.data,
-                                o["exitflag"].ctypes.data, o["iter"].ctypes.data, MEM_HOST, 0, 0)
+        o, r = _result(self.N, self.n, self.m, out, self.device)
         rc = lib().daqp_batch_solve(self._h, C.byref(r))
         if rc != 0:
             raise RuntimeError(f"daqp_batch_solve failed ({rc}): {_lib.last_error()}")
         self._out_keep = [o]
         return o
-
-    _BW_KEYS = ("dz", "dbupper", "dblower", "qsoft", "usoft", "usoft_id")
 
     def backward(self, grad_x, out="torch", nullspace=False, grad_lam=None):
         """The adjoint of the last solve (daqp_batch_backward, include/daqp_amd.h): for grad_x = dl/dx of shape (N, n) returns
@@ -339,67 +383,13 @@ class BatchModel:
         N, n, m, ns = self.N, self.n, self.m, self.ns
         if nullspace not in (False, True, "all"):
             raise ValueError('nullspace must be False, True or "all"')
+        gx = ("grad_x", grad_x, (N, n))
         if grad_lam is not None:
-            return self._backward_dual(grad_x, grad_lam, out, -1 if nullspace is False else (1 if nullspace == "all" else 0))
-        keep = []
-        if out == "torch":
-            dev = torch.device("cuda", self.device)
-            g = torch.as_tensor(grad_x, dtype=torch.float64, device=dev).contiguous()
-            if tuple(g.shape) != (N, n):
-                raise ValueError(f"grad_x must have shape {(N, n)}")
-            keep.append(g)
-            o = dict(dz=torch.empty((N, n), dtype=torch.float64, device=dev), dbupper=torch.empty((N, m), dtype=torch.float64, device=dev),
-                     dblower=torch.empty((N, m), dtype=torch.float64, device=dev), status=torch.empty(N, dtype=torch.int32, device=dev))
-            if ns > 0:
-                o.update(qsoft=torch.empty((N, m), dtype=torch.float64, device=dev), usoft=torch.empty((N, ns, n), dtype=torch.float64, device=dev),
-                         usoft_id=torch.empty((N, ns), dtype=torch.int32, device=dev))
-            ptrs = [g.data_ptr()] + [o[k].data_ptr() for k in self._BW_KEYS[:3 if (ns == 0 or nullspace) else 6]] + [o["status"].data_ptr()]
-            mem = MEM_DEVICE
-        else:
-            g = grad_x.detach().cpu().numpy() if _is_torch(grad_x) else grad_x
-            g = np.ascontiguousarray(g, dtype=np.float64)
-            if g.shape != (N, n):
-                raise ValueError(f"grad_x must have shape {(N, n)}")
-            o = dict(dz=np.empty((N, n)), dbupper=np.empty((N, m)), dblower=np.empty((N, m)), status=np.empty(N, np.int32))
-            if ns > 0:
-                o.update(qsoft=np.empty((N, m)), usoft=np.empty((N, ns, n)), usoft_id=np.empty((N, ns), np.int32))
-            ptrs = [g.ctypes.data] + [o[k].ctypes.data for k in self._BW_KEYS[:3 if (ns == 0 or nullspace) else 6]] + [o["status"].ctypes.data]
-            mem = MEM_HOST
-        if nullspace:
-            entry = "daqp_batch_backward_nullspace"      # (refuses ns_max > 0 itself)
-            rc = lib().daqp_batch_backward_nullspace(self._h, *ptrs, 1 if nullspace == "all" else 0, mem)
-        else:
-            entry = "daqp_batch_backward" if ns == 0 else "daqp_batch_backward_soft"
-            rc = getattr(lib(), entry)(self._h, *ptrs, mem)
-        if rc != 0:
-            raise RuntimeError(f"{entry} failed ({rc}): {_lib.last_error()}")
-        self._bw_keep = [keep, o]      # the launch reads / writes them after this call has returned
-        return o
-
-    def _backward_dual(self, grad_x, grad_lam, out, which):
-        N, n, m = self.N, self.n, self.m
-        if out == "torch":
-            dev = torch.device("cuda", self.device)
-            conv = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
-            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-            ptr = lambda a: None if a is None else a.data_ptr()
-            f64, i32, mem = torch.float64, torch.int32, MEM_DEVICE
-        else:
-            conv = lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64)
-            new = lambda shape, dtype: np.empty(shape, dtype)
-            ptr = lambda a: None if a is None else a.ctypes.data
-            f64, i32, mem = np.float64, np.int32, MEM_HOST
-        g, gl = conv(grad_x), conv(grad_lam)
-        if g is not None and tuple(g.shape) != (N, n):
-            raise ValueError(f"grad_x must have shape {(N, n)}")
-        if tuple(gl.shape) != (N, m):
-            raise ValueError(f"grad_lam must have shape {(N, m)}")
-        o = dict(dz=new((N, n), f64), dbupper=new((N, m), f64), dblower=new((N, m), f64), status=new((N,), i32))
-        rc = lib().daqp_batch_backward_dual(self._h, ptr(g), ptr(gl), ptr(o["dz"]), ptr(o["dbupper"]), ptr(o["dblower"]), ptr(o["status"]), which, mem)
-        if rc != 0:
-            raise RuntimeError(f"daqp_batch_backward_dual failed ({rc}): {_lib.last_error()}")
-        self._bw_keep = [[g, gl], o]      # the launch reads / writes them after this call has returned
-        return o
+            return _adjoint(self, out, "daqp_batch_backward_dual", (self._h,), (gx, ("grad_lam", grad_lam, (N, m))),
+                            which=-1 if nullspace is False else (1 if nullspace == "all" else 0))
+        if nullspace:      # (the entry refuses ns_max > 0 itself)
+            return _adjoint(self, out, "daqp_batch_backward_nullspace", (self._h,), (gx,), which=1 if nullspace == "all" else 0)
+        return _adjoint(self, out, "daqp_batch_backward" if ns == 0 else "daqp_batch_backward_soft", (self._h,), (gx,), soft=ns > 0)
 
     def backward_soft(self, grad_x=None, grad_lam=None, grad_slack=None, lam=None, out="torch"):
         """The adjoint of the last solve of a model with soft rows for a loss l(x, lam, fval, soft_slack)
@@ -411,29 +401,9 @@ class BatchModel:
         grad_slack lam_k^2 - 1/2 grad_fval lam_k^2 (daqp_amd.layer.soft_gradient_terms, dsig_extra).  Without grad_lam and grad_slack
         the result is that of backward(grad_x), bit for bit.  out='torch': device tensors in and out, nothing waits; out='numpy': host
         arrays."""
-        N, n, m, ns = self.N, self.n, self.m, self.ns
-        if out == "torch":
-            dev = torch.device("cuda", self.device)
-            conv = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
-            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-            ptr = lambda a: None if a is None else a.data_ptr()
-            f64, i32, mem = torch.float64, torch.int32, MEM_DEVICE
-        else:
-            conv = lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64)
-            new = lambda shape, dtype: np.empty(shape, dtype)
-            ptr = lambda a: None if a is None else a.ctypes.data
-            f64, i32, mem = np.float64, np.int32, MEM_HOST
-        ins = [conv(grad_x), conv(grad_lam), conv(grad_slack), conv(lam)]
-        for name, a, shape in zip(("grad_x", "grad_lam", "grad_slack", "lam"), ins, ((N, n), (N, m), (N,), (N, m))):
-            if a is not None and tuple(a.shape) != shape:
-                raise ValueError(f"{name} must have shape {shape}")
-        o = dict(dz=new((N, n), f64), dbupper=new((N, m), f64), dblower=new((N, m), f64), status=new((N,), i32),
-                 qsoft=new((N, m), f64), usoft=new((N, ns, n), f64), usoft_id=new((N, ns), i32))
-        rc = lib().daqp_batch_backward_soft_dual(self._h, *[ptr(a) for a in ins], *[ptr(o[k]) for k in self._BW_KEYS], ptr(o["status"]), mem)
-        if rc != 0:
-            raise RuntimeError(f"daqp_batch_backward_soft_dual failed ({rc}): {_lib.last_error()}")
-        self._bw_keep = [ins, o]      # the launch reads / writes them after this call has returned
-        return o
+        N, n, m = self.N, self.n, self.m
+        return _adjoint(self, out, "daqp_batch_backward_soft_dual", (self._h,), (("grad_x", grad_x, (N, n)), ("grad_lam", grad_lam, (N, m)),
+                                                                               ("grad_slack", grad_slack, (N,)), ("lam", lam, (N, m))), soft=True)
 
     def certify(self, res, out=None):
         """certify_batch on the inputs this model reads (the device tensors given to setup / setup_shared / update, kept in place)
@@ -644,21 +614,6 @@ class EliminatedBatchModel:
         except Exception:
             pass
 
-    @staticmethod
-    def _pointers(arrays):
-        """pointers and the one memory side of (name, array, dtype) triples; what must stay referenced comes back by name"""
-        keep, ptrs, mems = {}, [], set()
-        for name, a, dt in arrays:
-            tmp = []
-            p, mem = _ptr(a, dt, tmp)
-            ptrs.append(p)
-            if mem is not None:
-                mems.add(mem)
-                keep[name] = tmp[0]
-        if len(mems) > 1:
-            raise ValueError("mix of host and device arrays in one call")
-        return ptrs, (mems.pop() if mems else MEM_HOST), keep
-
     def _read_flags(self):
         fl = np.zeros(self.N, np.int32)
         rc = lib().daqp_batch_elimination_flags(self._el, _ip(fl))
@@ -674,8 +629,7 @@ class EliminatedBatchModel:
 
     def eliminate(self, H, f, A, bupper, blower, sense=None):
         """the first half of setup(): daqp_batch_eliminate alone (a new handle; follow with setup_reduced)"""
-        ptrs, mem, keep = self._pointers((("H", H, np.float64), ("f", f, np.float64), ("A", A if self.m > self.ms else None, np.float64),
-                                          ("bupper", bupper, np.float64), ("blower", blower, np.float64), ("sense", sense, np.int32)))
+        ptrs, mem, keep = _problem_pointers(H, f, A if self.m > self.ms else None, bupper, blower, sense)
         p = DAQPBatchProblem(self.N, self.n, self.m, self.ms, *ptrs, mem)
         if self._el:
             lib().daqp_batch_elimination_free(self._el)
@@ -705,7 +659,7 @@ class EliminatedBatchModel:
             raise ValueError(f"EliminatedBatchModel.update takes f, bupper and blower only; for {sorted(other)} call setup again")
         if not self._el:
             raise RuntimeError("EliminatedBatchModel.update called before setup")
-        ptrs, mem, keep = self._pointers((("f", f, np.float64), ("bupper", bupper, np.float64), ("blower", blower, np.float64)))
+        ptrs, mem, keep = _pointers((("f", f, np.float64), ("bupper", bupper, np.float64), ("blower", blower, np.float64)))
         rc = lib().daqp_batch_eliminate_update(self._el, *ptrs, mem)
         if rc != 0:
             raise RuntimeError(f"daqp_batch_eliminate_update failed ({rc}): {_lib.last_error()}")
@@ -725,20 +679,9 @@ class EliminatedBatchModel:
 
     def expand(self, r, out="numpy"):
         """the second half of solve(): daqp_batch_expand of a result dict of .reduced.solve(out=out)"""
-        N, n, m = self.N, self.n, self.m
-        if out == "torch":
-            dev = torch.device("cuda", self.device)
-            o = dict(x=torch.empty((N, n), dtype=torch.float64, device=dev), lam=torch.empty((N, m), dtype=torch.float64, device=dev),
-                     fval=torch.empty(N, dtype=torch.float64, device=dev), soft_slack=torch.empty(N, dtype=torch.float64, device=dev),
-                     exitflag=torch.empty(N, dtype=torch.int32, device=dev), iter=torch.empty(N, dtype=torch.int32, device=dev))
-            ptr, mem = (lambda t: t.data_ptr()), MEM_DEVICE
-        else:
-            o = dict(x=np.empty((N, n)), lam=np.empty((N, m)), fval=np.empty(N), soft_slack=np.empty(N),
-                     exitflag=np.empty(N, np.int32), iter=np.empty(N, np.int32))
-            ptr, mem = (lambda a: a.ctypes.data), MEM_HOST
-        keys = ("x", "lam", "fval", "soft_slack", "exitflag", "iter")
-        rr = DAQPBatchResult(*[ptr(r[k]) for k in keys], mem, 0, 0)
-        fr = DAQPBatchResult(*[ptr(o[k]) for k in keys], mem, 0, 0)
+        k = _kit(out, self.device)
+        o, fr = _result(self.N, self.n, self.m, out, self.device)
+        rr = DAQPBatchResult(*[k.ptr(r[key]) for key in _RESULT_KEYS], k.mem, 0, 0)
         rc = lib().daqp_batch_expand(self._el, C.byref(rr), C.byref(fr))
         if rc != 0:
             raise RuntimeError(f"daqp_batch_expand failed ({rc}): {_lib.last_error()}")
@@ -765,33 +708,11 @@ class EliminatedBatchModel:
             raise ValueError('nullspace must be False, True or "all"')
         if grad_x is None and grad_lam is None:
             raise ValueError("grad_x and grad_lam are both None: there is nothing to differentiate")
-        N, n, m = self.N, self.n, self.m
         if out is None:
             out = "torch" if any(_is_torch(a) and a.is_cuda for a in (grad_x, grad_lam)) else "numpy"
-        if out == "torch":
-            dev = torch.device("cuda", self.device)
-            conv = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float64, device=dev).contiguous()
-            new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
-            ptr = lambda a: None if a is None else a.data_ptr()
-            f64, i32, mem = torch.float64, torch.int32, MEM_DEVICE
-        else:
-            conv = lambda a: None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float64)
-            new = lambda shape, dtype: np.empty(shape, dtype)
-            ptr = lambda a: None if a is None else a.ctypes.data
-            f64, i32, mem = np.float64, np.int32, MEM_HOST
-        g, gl = conv(grad_x), conv(grad_lam)
-        if g is not None and tuple(g.shape) != (N, n):
-            raise ValueError(f"grad_x must have shape {(N, n)}")
-        if gl is not None and tuple(gl.shape) != (N, m):
-            raise ValueError(f"grad_lam must have shape {(N, m)}")
-        o = dict(dz=new((N, n), f64), dbupper=new((N, m), f64), dblower=new((N, m), f64), status=new((N,), i32))
-        which = -1 if nullspace is False else (1 if nullspace == "all" else 0)
-        rc = lib().daqp_batch_eliminate_backward(self._el, self.reduced._h, ptr(g), ptr(gl), ptr(o["dz"]), ptr(o["dbupper"]), ptr(o["dblower"]),
-                                                 ptr(o["status"]), which, mem)
-        if rc != 0:
-            raise RuntimeError(f"daqp_batch_eliminate_backward failed ({rc}): {_lib.last_error()}")
-        self._bw_keep = [[g, gl], o]      # the launches read / write them after this call has returned
-        return o
+        return _adjoint(self, out, "daqp_batch_eliminate_backward", (self._el, self.reduced._h),
+                        (("grad_x", grad_x, (self.N, self.n)), ("grad_lam", grad_lam, (self.N, self.m))),
+                        which=-1 if nullspace is False else (1 if nullspace == "all" else 0))
 
     def certify(self, res, out=None):
         """certify_batch on the caller's FULL problem and res["x"], res["lam"] of a solve()"""
@@ -861,11 +782,7 @@ def solve_batch(H, f, A, bupper, blower=None, sense=None, ms=None, out="numpy", 
             em.close()
         return res
     if N == 0:   # an empty batch is a valid (empty) answer, as it is for daqp_quadprog_batch
-        if out == "torch" and _is_torch(f):
-            z = lambda *sh, dt=torch.float64: torch.zeros(sh, dtype=dt, device=f.device)
-            return dict(x=z(0, n), lam=z(0, m), fval=z(0), soft_slack=z(0), exitflag=z(0, dt=torch.int32), iter=z(0, dt=torch.int32))
-        return dict(x=np.zeros((0, n)), lam=np.zeros((0, m)), fval=np.zeros(0), soft_slack=np.zeros(0),
-                    exitflag=np.zeros(0, np.int32), iter=np.zeros(0, np.int32))
+        return _result(0, n, m, "torch", f.device)[0] if out == "torch" and _is_torch(f) else _result(0, n, m, "numpy", None)[0]
     ns = 0
     if sense is not None:
         s = sense.cpu().numpy() if _is_torch(sense) else np.asarray(sense)

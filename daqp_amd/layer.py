@@ -9,6 +9,9 @@ Forward is a BatchModel setup + solve on the inputs' device and current stream. 
 
     dl/df = -dz      dl/dH = -1/2 (dz x' + x dz')      dl/dA_i = -(lam_i dz + dnu_i x)'      dl/dbupper, dl/dblower = dbupper, dblower
 
+Every route below ends in those torch operations, and they are written once: assemble_gradients (pure torch, any device, no
+library) turns what a model's backward returned into (dH, df, dA, dbupper, dblower, drho).
+
 An active SOFT row k sits at c_k x - b_k = rho_soft q_k lam_k, q_k = c_k H^-1 c_k': the system's (2,2) block is -S, S = diag(rho_soft
 q_k), and since q_k depends on H and A their gradients gain a term each (soft_gradient_terms below; dsig_k = dnu_k lam_k, u_k = H^-1 c_k'):
 
@@ -82,345 +85,193 @@ def soft_gradient_terms(lam, dnu, qsoft, usoft, usoft_id, rho_soft, ms, dsig_ext
     return dict(dH=dH, dA=dA, drho=drho)
 
 
+def assemble_gradients(x, lam, ms, o, status, need, shared=False, g_fval=None, g_slack=None, rho=0.0, eq=None):
+    """(dH, df, dA, dbupper, dblower, drho) of a loss l(x, lam, fval, soft_slack) from the adjoint solution of ITS g_x, g_lam (and
+    g_slack): the formulas of the module docstring, once for every route of qp_layer.  Pure torch, any device, no library.
+
+        x (N, n), lam (N, m)   of the solve; ms: the number of simple bounds (rows ms.. of lam belong to A)
+        o                      the dict a model's backward / backward_soft returned -- dz (N, n), dbupper, dblower (N, m) and, of a model
+                               with SOFT rows, qsoft (N, m), usoft (N, ns, n), usoft_id (N, ns) -- or None: nothing was launched
+        status (N,)            0, or why that problem has no derivative: g_fval and g_slack are zeroed there (o is zero there already)
+        need                   six booleans, for H, f, A, bupper, blower, rho: what is not needed is not computed and comes back None
+        shared                 one H (n, n) and one A (m - ms, n) for the batch: dH and dA are the sums over the batch
+        g_fval, g_slack (N,)   dl/dfval, dl/dsoft_slack, or None
+        rho                    rho_soft, the float
+        eq                     index tensor of the equality rows of an eliminated batch: the -g_fval lam term of such a row goes to
+                               dbupper whatever its sign, and dblower gets zero there
+
+    In this order: the five formulas on o; the q_k-dependence terms of soft_gradient_terms with dsig_extra = g_slack lam^2 - 1/2 g_fval
+    lam^2 (only where o has SOFT slots and H, A or rho is needed); the envelope terms of g_fval; the batch sum of a shared dH.  drho
+    is the sum over the batch (rho_soft is one number), None when no q_k-dependence term was formed."""
+    nH, nf, nA, nbu, nbl, nrho = need
+    gH = gf = gA = gbu = gbl = grho = None
+    add = lambda a, b: b if a is None else a + b
+    ok = status == 0      # a problem without a derivative gets zero gradients from every term
+    gv = None if g_fval is None else g_fval * ok
+    if o is not None:
+        dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
+        soft = None
+        if o.get("usoft") is not None and o["usoft"].shape[1] > 0 and (nH or nA or nrho):      # the q_k-dependence of S
+            extra = None
+            if g_slack is not None:
+                extra = (g_slack * ok)[:, None] * lam * lam
+            if gv is not None:
+                extra = add(extra, -0.5 * gv[:, None] * lam * lam)
+            soft = soft_gradient_terms(lam, dbu + dbl, o["qsoft"], o["usoft"], o["usoft_id"], rho, ms, dsig_extra=extra)
+        if nH:
+            gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
+            if soft is not None:
+                gH = gH + soft["dH"]
+        if nf:
+            gf = -dz
+        if nA:
+            lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
+            gA = -(lg.t() @ dz + ng.t() @ x) if shared else -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
+            if soft is not None:
+                gA = gA + (soft["dA"].sum(0) if shared else soft["dA"])
+        if nbu:
+            gbu = dbu
+        if nbl:
+            gbl = dbl
+        if nrho and soft is not None:
+            grho = soft["drho"].sum()
+    if gv is not None:
+        if nH:
+            gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
+        if nf:
+            gf = add(gf, gv[:, None] * x)
+        if nA:
+            lg = gv[:, None] * lam[:, ms:]
+            gA = add(gA, lg.t() @ x if shared else lg[:, :, None] * x[:, None, :])
+        up, lo = lam.clamp(min=0.0), lam.clamp(max=0.0)      # lam_i > 0: the row sits at (or, SOFT, beyond) its upper bound;
+        if eq is not None:
+            up[:, eq], lo[:, eq] = lam[:, eq], 0.0            # an equality row: everything to bupper
+        if nbu:
+            gbu = add(gbu, -gv[:, None] * up)
+        if nbl:
+            gbl = add(gbl, -gv[:, None] * lo)
+    if shared and gH is not None:
+        gH = gH.sum(0)
+    return gH, gf, gA, gbu, gbl, grho
+
+
+def _backward_status(o, exitflag, info, strict):
+    """status of a backward: the launch's, or -- nothing launched: the envelope terms exist wherever the solve ended optimal -- the exit
+    flag with 1 turned into 0.  Written into info; strict raises on the first problem without a derivative."""
+    status = o["status"] if o is not None else torch.where(exitflag == 1, torch.zeros_like(exitflag), exitflag)
+    if info is not None:
+        info["status"] = status
+    if strict:
+        badq = torch.nonzero(status).flatten()
+        if badq.numel():
+            q = int(badq[0])
+            raise RuntimeError(f"qp_layer: {badq.numel()} of {status.numel()} problems have no derivative (first: problem {q}, status "
+                               f"{int(status[q])}); strict=False gives them zero gradients")
+    return status
+
+
+def _prepare(H, f, A, bupper, blower, ms, sense, lp):
+    """what forward checks and converts whatever model it builds: (N, n, m, ms, shared, ns_max, [H, f, A, bupper, blower] detached
+    float64 contiguous, sense (N, m) int32 or None).  lp: H=None is an LP batch (it has no plant to share)."""
+    if not f.is_cuda:
+        raise ValueError("qp_layer needs its inputs on the GPU")
+    N, n = f.shape
+    m = bupper.shape[1]
+    if H is None and lp:
+        if A is not None and A.dim() == 2:
+            raise ValueError("H=None (an LP batch) goes with A of shape (N, mA, n): a shared-plant LP is not supported")
+        shared = False
+    else:
+        shared = H.dim() == 2
+    if A is not None and H is not None and (A.dim() == 2) != shared:
+        raise ValueError("H of shape (n, n) goes with A of shape (mA, n): one plant for the whole batch")
+    mA = 0 if A is None else A.shape[-2]
+    ms = m - mA if ms is None else int(ms)
+    if ms + mA != m:
+        raise ValueError(f"m = {m} bounds for ms = {ms} simple bounds and {mA} rows of A")
+    c = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
+    bl = torch.full_like(bupper, -INF).detach() if blower is None else blower
+    ns_max = 0
+    if sense is not None:
+        sense = torch.as_tensor(sense).detach().to(device=f.device, dtype=torch.int32)
+        if sense.dim() == 1:
+            sense = sense.expand(N, m)
+        if tuple(sense.shape) != (N, m):
+            raise ValueError(f"sense must have shape {(N, m)} or {(m,)}")
+        sense = sense.contiguous()
+        ns_max = int(((sense & SOFT) != 0).sum(1).max())
+    return N, n, m, ms, shared, ns_max, [c(H), c(f), c(A), c(bupper), c(bl)], sense
+
+
 class _QPLayer(torch.autograd.Function):
+    """every route of qp_layer.  route: "x" (the default call), "names" (returns=...), "soft" (soft_returns=True) or "eq" (eq_rows=...):
+    it picks the model forward builds and the adjoint call backward makes; names: what forward returns, always as a tuple."""
+
     @staticmethod
-    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, rho_soft, nullspace=False, returns=None, soft_returns=False):
-        if not f.is_cuda:
-            raise ValueError("qp_layer needs its inputs on the GPU")
-        N, n = f.shape
-        m = bupper.shape[1]
-        if H is None and nullspace:      # an LP batch
-            if A is not None and A.dim() == 2:
-                raise ValueError("H=None (an LP batch) goes with A of shape (N, mA, n): a shared-plant LP is not supported")
-            shared = False
-        else:
-            shared = H.dim() == 2
-        if A is not None and H is not None and (A.dim() == 2) != shared:
-            raise ValueError("H of shape (n, n) goes with A of shape (mA, n): one plant for the whole batch")
-        mA = 0 if A is None else A.shape[-2]
-        ms = m - mA if ms is None else int(ms)
-        if ms + mA != m:
-            raise ValueError(f"m = {m} bounds for ms = {ms} simple bounds and {mA} rows of A")
-        c = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
-        bl = torch.full_like(bupper, -INF).detach() if blower is None else blower
-        ns_max = 0
-        if sense is not None:
-            sense = torch.as_tensor(sense).detach().to(device=f.device, dtype=torch.int32)
-            if sense.dim() == 1:
-                sense = sense.expand(N, m)
-            if tuple(sense.shape) != (N, m):
-                raise ValueError(f"sense must have shape {(N, m)} or {(m,)}")
-            sense = sense.contiguous()
-            ns_max = int(((sense & SOFT) != 0).sum(1).max())
+    def forward(ctx, H, f, A, bupper, blower, rho_soft, ms, strict, info, settings, sense, nullspace, names, route, eq_rows):
+        N, n, m, ms, shared, ns_max, arrays, sense = _prepare(H, f, A, bupper, blower, ms, sense, lp=nullspace or route == "eq")
         settings = dict(settings)
         if rho_soft is not None:
             settings["rho_soft"] = float(rho_soft)
         with torch.cuda.device(f.device):      # the model takes that device's current stream
-            bm = BatchModel(N, n, m, ms, ns_max, device=f.device.index, **settings)
-            if shared:
-                bm.setup_shared(c(H), c(f), c(A), c(bupper), c(bl), sense)
+            if route == "eq":
+                model = EliminatedBatchModel(N, n, m, ms, eq_rows, 0, settings=settings, device=f.device.index)
+                model.setup(*arrays, sense, init_mask=UPDATE_unconstrained)
             else:
-                bm.setup(c(H), c(f), c(A), c(bupper), c(bl), sense, init_mask=UPDATE_unconstrained)
-            r = bm.solve(out="torch")
-        ctx.bm, ctx.x, ctx.lam = bm, r["x"], r["lam"]
-        ctx.rho = bm._settings.rho_soft
+                model = BatchModel(N, n, m, ms, ns_max, device=f.device.index, **settings)
+                if shared:
+                    model.setup_shared(*arrays, sense)
+                else:
+                    model.setup(*arrays, sense, init_mask=UPDATE_unconstrained)
+            r = model.solve(out="torch")
+        ctx.model, ctx.x, ctx.lam, ctx.exitflag = model, r["x"], r["lam"], r["exitflag"]
+        ctx.rho = model._settings.rho_soft
         ctx.rho_like = rho_soft if isinstance(rho_soft, torch.Tensor) else None
         ctx.ms, ctx.shared, ctx.strict, ctx.info = ms, shared, strict, info
-        ctx.nullspace = bool(nullspace)
-        ctx.returns, ctx.exitflag, ctx.soft_returns = returns, r["exitflag"], bool(soft_returns)
+        ctx.nullspace, ctx.names, ctx.route = bool(nullspace), names, route
+        ctx.eq = torch.as_tensor(model.eq_rows, dtype=torch.long, device=f.device) if route == "eq" else None
         if info is not None:
             info["exitflag"] = r["exitflag"]
             info["lam"] = r["lam"]
-        if returns is not None:      # a tuple of names: x, lam, fval in the caller's order; a gradient nobody sent stays None
-            ctx.set_materialize_grads(False)
-            return tuple(r[k].clone() for k in returns)
-        return r["x"].clone()      # (the kept copy is what backward multiplies with, whatever the caller does to its own)
+        ctx.set_materialize_grads(False)      # a gradient nobody sent stays None
+        return tuple(r[k].clone() for k in names)      # (the kept copies are what backward multiplies with, whatever the caller does to its own)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
-        if ctx.returns is not None:
-            g = dict(zip(ctx.returns, grads))
-            return _QPLayer._backward_soft_returns(ctx, g) if ctx.soft_returns else _QPLayer._backward_returns(ctx, g)
-        grad_x, = grads
-        with torch.cuda.device(x.device):
-            o = bm.backward(grad_x.to(torch.float64).contiguous(), out="torch", nullspace=ctx.nullspace)
-        status = o["status"]
-        if ctx.info is not None:
-            ctx.info["status"] = status
-        if ctx.strict:
-            badq = torch.nonzero(status).flatten()
-            if badq.numel():
-                q = int(badq[0])
-                raise RuntimeError(f"qp_layer: {badq.numel()} of {bm.N} problems have no derivative (first: problem {q}, status "
-                                   f"{int(status[q])}); strict=False gives them zero gradients")
-        dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
-        need = ctx.needs_input_grad
-        gH = gf = gA = gbu = gbl = grho = None
-        soft = None
-        if "usoft" in o and (need[0] or need[2] or need[10]):      # the q_k-dependence of S
-            soft = soft_gradient_terms(lam, dbu + dbl, o["qsoft"], o["usoft"], o["usoft_id"], ctx.rho, ms)
-        if need[0]:
-            gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
-            if soft is not None:
-                gH = gH + soft["dH"]
-            if ctx.shared:
-                gH = gH.sum(0)
-        if need[1]:
-            gf = -dz
-        if need[2]:
-            lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
-            if ctx.shared:
-                gA = -(lg.t() @ dz + ng.t() @ x)
-            else:
-                gA = -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
-            if soft is not None:
-                gA = gA + (soft["dA"].sum(0) if ctx.shared else soft["dA"])
-        if need[3]:
-            gbu = dbu
-        if need[4]:
-            gbl = dbl
-        if need[10]:
-            like = ctx.rho_like
-            grho = soft["drho"].sum() if soft is not None else torch.zeros((), dtype=torch.float64, device=x.device)
-            grho = grho.to(device=like.device, dtype=like.dtype).reshape(like.shape)
-        return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho, None
-
-    @staticmethod
-    def _backward_returns(ctx, g):
-        """backward of returns=(...): one adjoint launch with g_x and g_lam (none when only fval carries a gradient), the formulas of
-        the module docstring, then the envelope terms of g_fval"""
-        bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
-        c = lambda t: None if t is None else t.to(torch.float64).contiguous()
-        gx, gl, gv = c(g.get("x")), c(g.get("lam")), c(g.get("fval"))
-        none = (None,) * 13
-        if gx is None and gl is None and gv is None:
-            return none
-        o = None
-        with torch.cuda.device(x.device):
-            if gl is not None:
-                o = bm.backward(gx, out="torch", nullspace=ctx.nullspace, grad_lam=gl)
-            elif gx is not None:
-                o = bm.backward(gx, out="torch", nullspace=ctx.nullspace)
-        # (no launch: the envelope terms exist wherever the solve ended optimal)
-        status = o["status"] if o is not None else torch.where(ctx.exitflag == 1, torch.zeros_like(ctx.exitflag), ctx.exitflag)
-        if ctx.info is not None:
-            ctx.info["status"] = status
-        if ctx.strict:
-            badq = torch.nonzero(status).flatten()
-            if badq.numel():
-                q = int(badq[0])
-                raise RuntimeError(f"qp_layer: {badq.numel()} of {bm.N} problems have no derivative (first: problem {q}, status "
-                                   f"{int(status[q])}); strict=False gives them zero gradients")
-        need = ctx.needs_input_grad
-        gH = gf = gA = gbu = gbl = None
-        add = lambda a, b: b if a is None else a + b
-        if o is not None:
-            dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
-            if need[0]:
-                gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
-            if need[1]:
-                gf = -dz
-            if need[2]:
-                lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
-                gA = -(lg.t() @ dz + ng.t() @ x) if ctx.shared else -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
-            if need[3]:
-                gbu = dbu
-            if need[4]:
-                gbl = dbl
-        if gv is not None:
-            gv = gv * (status == 0)      # a problem without a derivative gets zero gradients here as well
-            if need[0]:
-                gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
-            if need[1]:
-                gf = add(gf, gv[:, None] * x)
-            if need[2]:
-                lg = gv[:, None] * lam[:, ms:]
-                gA = add(gA, lg.t() @ x if ctx.shared else lg[:, :, None] * x[:, None, :])
-            if need[3]:
-                gbu = add(gbu, -gv[:, None] * lam.clamp(min=0.0))      # lam_i > 0: the row sits at its upper bound
-            if need[4]:
-                gbl = add(gbl, -gv[:, None] * lam.clamp(max=0.0))
-        if need[0] and ctx.shared and gH is not None and gH.dim() == 3:
-            gH = gH.sum(0)
-        return gH, gf, gA, gbu, gbl, None, None, None, None, None, None, None, None
-
-    @staticmethod
-    def _backward_soft_returns(ctx, g):
-        """backward of returns=(...) with soft_returns=True: ONE daqp_batch_backward_soft_dual launch with g_x, g_lam and g_slack, the
-        five formulas, the q_k-dependence terms with dsig_k = dnu_k lam_k + g_slack lam_k^2 - 1/2 g_fval lam_k^2, then the envelope
-        terms of g_fval.  A model without SOFT rows has soft_slack = 0: g_slack meets nothing."""
-        bm, x, lam, ms = ctx.bm, ctx.x, ctx.lam, ctx.ms
+        model, x, lam, route = ctx.model, ctx.x, ctx.lam, ctx.route
+        g = dict(zip(ctx.names, grads))
         c = lambda t: None if t is None else t.to(torch.float64).contiguous()
         gx, gl, gv, gs = c(g.get("x")), c(g.get("lam")), c(g.get("fval")), c(g.get("soft_slack"))
-        soft = bm.ns > 0
-        if not soft:
+        if model.ns == 0:      # soft_slack = 0: g_slack meets nothing
             gs = None
+        none = (None,) * 15
         if gx is None and gl is None and gv is None and gs is None:
-            return (None,) * 14
-        o = None
+            return none
+        o = None      # stays None when only fval carries a gradient: its terms need no solve
         with torch.cuda.device(x.device):
-            if soft and gx is None and gl is None and gs is None:      # g_fval alone: its dsig term still needs q_k and u_k
-                o = bm.backward_soft(torch.zeros_like(x), out="torch")
-            elif gx is not None or gl is not None or gs is not None:
-                o = bm.backward_soft(gx, gl, gs, lam if gs is not None else None, out="torch")
-        # (no launch: the envelope terms exist wherever the solve ended optimal)
-        status = o["status"] if o is not None else torch.where(ctx.exitflag == 1, torch.zeros_like(ctx.exitflag), ctx.exitflag)
-        if ctx.info is not None:
-            ctx.info["status"] = status
-        if ctx.strict:
-            badq = torch.nonzero(status).flatten()
-            if badq.numel():
-                q = int(badq[0])
-                raise RuntimeError(f"qp_layer: {badq.numel()} of {bm.N} problems have no derivative (first: problem {q}, status "
-                                   f"{int(status[q])}); strict=False gives them zero gradients")
-        need = ctx.needs_input_grad
-        gH = gf = gA = gbu = gbl = grho = None
-        add = lambda a, b: b if a is None else a + b
-        ok = status == 0      # a problem without a derivative gets zero gradients from every term
-        if gv is not None:
-            gv = gv * ok
-        if o is not None:
-            dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
-            sterm = None
-            if soft and (need[0] or need[2] or need[10]):      # the q_k-dependence of S
-                extra = None
-                if gs is not None:
-                    extra = (gs * ok)[:, None] * lam * lam
-                if gv is not None:
-                    extra = add(extra, -0.5 * gv[:, None] * lam * lam)
-                sterm = soft_gradient_terms(lam, dbu + dbl, o["qsoft"], o["usoft"], o["usoft_id"], ctx.rho, ms, dsig_extra=extra)
-            if need[0]:
-                gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
-                if sterm is not None:
-                    gH = gH + sterm["dH"]
-            if need[1]:
-                gf = -dz
-            if need[2]:
-                lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
-                gA = -(lg.t() @ dz + ng.t() @ x) if ctx.shared else -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
-                if sterm is not None:
-                    gA = gA + (sterm["dA"].sum(0) if ctx.shared else sterm["dA"])
-            if need[3]:
-                gbu = dbu
-            if need[4]:
-                gbl = dbl
-            if need[10] and sterm is not None:
-                grho = sterm["drho"].sum()
-        if gv is not None:
-            if need[0]:
-                gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
-            if need[1]:
-                gf = add(gf, gv[:, None] * x)
-            if need[2]:
-                lg = gv[:, None] * lam[:, ms:]
-                gA = add(gA, lg.t() @ x if ctx.shared else lg[:, :, None] * x[:, None, :])
-            if need[3]:
-                gbu = add(gbu, -gv[:, None] * lam.clamp(min=0.0))      # lam_i > 0: the row sits at (or, SOFT, beyond) its upper bound
-            if need[4]:
-                gbl = add(gbl, -gv[:, None] * lam.clamp(max=0.0))
-        if need[0] and ctx.shared and gH is not None and gH.dim() == 3:
-            gH = gH.sum(0)
-        if need[10]:
+            if route == "soft":
+                if gx is not None or gl is not None or gs is not None:
+                    o = model.backward_soft(gx, gl, gs, lam if gs is not None else None, out="torch")
+                elif model.ns > 0:      # g_fval alone: its dsig term still needs q_k and u_k
+                    o = model.backward_soft(torch.zeros_like(x), out="torch")
+            elif route == "eq":
+                if gx is not None or gl is not None:
+                    o = model.backward(gx, grad_lam=gl, out="torch", nullspace=ctx.nullspace)
+            elif gl is not None:
+                o = model.backward(gx, out="torch", nullspace=ctx.nullspace, grad_lam=gl)
+            elif gx is not None:
+                o = model.backward(gx, out="torch", nullspace=ctx.nullspace)
+        status = _backward_status(o, ctx.exitflag, ctx.info, ctx.strict)
+        need = ctx.needs_input_grad[:6]
+        gH, gf, gA, gbu, gbl, grho = assemble_gradients(x, lam, ctx.ms, o, status, need, ctx.shared, gv, gs, ctx.rho, ctx.eq)
+        if need[5] and route != "names":      # (returns=... without soft_returns leaves a rho_soft tensor without a gradient)
             like = ctx.rho_like
             grho = torch.zeros((), dtype=torch.float64, device=x.device) if grho is None else grho
             grho = grho.to(device=like.device, dtype=like.dtype).reshape(like.shape)
-        return gH, gf, gA, gbu, gbl, None, None, None, None, None, grho, None, None, None
-
-
-class _EliminatedQPLayer(torch.autograd.Function):
-    """qp_layer(..., eq_rows=...): forward through an EliminatedBatchModel, backward through its adjoint"""
-
-    @staticmethod
-    def forward(ctx, H, f, A, bupper, blower, ms, strict, info, settings, sense, nullspace, returns, eq_rows):
-        if not f.is_cuda:
-            raise ValueError("qp_layer needs its inputs on the GPU")
-        N, n = f.shape
-        m = bupper.shape[1]
-        mA = 0 if A is None else A.shape[-2]
-        ms = m - mA if ms is None else int(ms)
-        if ms + mA != m:
-            raise ValueError(f"m = {m} bounds for ms = {ms} simple bounds and {mA} rows of A")
-        c = lambda t: None if t is None else t.detach().to(torch.float64).contiguous()
-        bl = torch.full_like(bupper, -INF).detach() if blower is None else blower
-        if sense is not None:
-            sense = torch.as_tensor(sense).detach().to(device=f.device, dtype=torch.int32)
-            if sense.dim() == 1:
-                sense = sense.expand(N, m)
-            if tuple(sense.shape) != (N, m):
-                raise ValueError(f"sense must have shape {(N, m)} or {(m,)}")
-            sense = sense.contiguous()
-        with torch.cuda.device(f.device):      # the model takes that device's current stream
-            em = EliminatedBatchModel(N, n, m, ms, eq_rows, 0, settings=dict(settings), device=f.device.index)
-            em.setup(c(H), c(f), c(A), c(bupper), c(bl), sense, init_mask=UPDATE_unconstrained)
-            r = em.solve(out="torch")
-        ctx.em, ctx.x, ctx.lam = em, r["x"], r["lam"]
-        ctx.ms, ctx.strict, ctx.info, ctx.nullspace = ms, strict, info, bool(nullspace)
-        ctx.returns, ctx.exitflag = returns, r["exitflag"]
-        ctx.eq = torch.as_tensor(em.eq_rows, dtype=torch.long, device=f.device)
-        if info is not None:
-            info["exitflag"] = r["exitflag"]
-            info["lam"] = r["lam"]
-        ctx.set_materialize_grads(False)
-        return tuple(r[k].clone() for k in returns)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *grads):
-        em, x, lam, ms = ctx.em, ctx.x, ctx.lam, ctx.ms
-        g = dict(zip(ctx.returns, grads))
-        c = lambda t: None if t is None else t.to(torch.float64).contiguous()
-        gx, gl, gv = c(g.get("x")), c(g.get("lam")), c(g.get("fval"))
-        none = (None,) * 13
-        if gx is None and gl is None and gv is None:
-            return none
-        o = None
-        if gx is not None or gl is not None:
-            with torch.cuda.device(x.device):
-                o = em.backward(gx, grad_lam=gl, out="torch", nullspace=ctx.nullspace)
-        # (no launch: the envelope terms exist wherever the solve ended optimal)
-        status = o["status"] if o is not None else torch.where(ctx.exitflag == 1, torch.zeros_like(ctx.exitflag), ctx.exitflag)
-        if ctx.info is not None:
-            ctx.info["status"] = status
-        if ctx.strict:
-            badq = torch.nonzero(status).flatten()
-            if badq.numel():
-                q = int(badq[0])
-                raise RuntimeError(f"qp_layer: {badq.numel()} of {em.N} problems have no derivative (first: problem {q}, status "
-                                   f"{int(status[q])}); strict=False gives them zero gradients")
-        need = ctx.needs_input_grad
-        gH = gf = gA = gbu = gbl = None
-        add = lambda a, b: b if a is None else a + b
-        if o is not None:
-            dz, dbu, dbl = o["dz"], o["dbupper"], o["dblower"]
-            if need[0]:
-                gH = -0.5 * (dz[:, :, None] * x[:, None, :] + x[:, :, None] * dz[:, None, :])
-            if need[1]:
-                gf = -dz
-            if need[2]:
-                lg, ng = lam[:, ms:], (dbu + dbl)[:, ms:]
-                gA = -(lg[:, :, None] * dz[:, None, :] + ng[:, :, None] * x[:, None, :])
-            if need[3]:
-                gbu = dbu
-            if need[4]:
-                gbl = dbl
-        if gv is not None:
-            gv = gv * (status == 0)      # a problem without a derivative gets zero gradients here as well
-            if need[0]:
-                gH = add(gH, 0.5 * gv[:, None, None] * x[:, :, None] * x[:, None, :])
-            if need[1]:
-                gf = add(gf, gv[:, None] * x)
-            if need[2]:
-                lg = gv[:, None] * lam[:, ms:]
-                gA = add(gA, lg[:, :, None] * x[:, None, :])
-            up, lo = lam.clamp(min=0.0), lam.clamp(max=0.0)      # lam_i > 0: the row sits at its upper bound;
-            up[:, ctx.eq], lo[:, ctx.eq] = lam[:, ctx.eq], 0.0     # an equality row: everything to bupper
-            if need[3]:
-                gbu = add(gbu, -gv[:, None] * up)
-            if need[4]:
-                gbl = add(gbl, -gv[:, None] * lo)
-        return gH, gf, gA, gbu, gbl, None, None, None, None, None, None, None, None
+        else:
+            grho = None
+        return (gH, gf, gA, gbu, gbl, grho) + none[6:]
 
 
 RETURNS = ("x", "lam", "fval")
@@ -472,34 +323,26 @@ def qp_layer(H, f, A, bupper, blower=None, ms=None, strict=True, info=None, sens
     sum, which is its gradient.  Raises ValueError for H or A of one shared plant (2-D) and for SOFT rows.  Without eq_rows the layer
     is what it was."""
     has_soft = sense is not None and bool(((torch.as_tensor(sense) & SOFT) != 0).any())
-    if soft_returns:
+    route = "soft" if soft_returns else "eq" if eq_rows is not None else "x" if isinstance(returns, str) and returns == "x" else "names"
+    if route == "soft":
         if eq_rows is not None or nullspace:
             raise ValueError("qp_layer: soft_returns=True goes with neither eq_rows nor nullspace: SOFT rows are refused on both routes")
-        names = (returns,) if isinstance(returns, str) else tuple(returns)
-        if not names or len(set(names)) != len(names) or any(k not in SOFT_RETURNS for k in names):
-            raise ValueError(f'qp_layer: returns must be distinct names out of {SOFT_RETURNS} with soft_returns=True (got {returns!r})')
-        out = _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, False, names, True)
-        return out[0] if isinstance(returns, str) else out
-    if eq_rows is not None:
+    elif route == "eq":
         if has_soft:
             raise ValueError("qp_layer: eq_rows does not take SOFT rows: a SOFT kept row is weighted by the reduced q_k")
         if (H is not None and H.dim() == 2) or (A is not None and A.dim() == 2):
             raise ValueError("qp_layer: eq_rows does not take one shared H / A: the elimination needs H (N, n, n) and A (N, mA, n)")
         if rho_soft is not None:
             raise ValueError("qp_layer: eq_rows does not take rho_soft: there are no SOFT rows to weigh")
-        names = (returns,) if isinstance(returns, str) else tuple(returns)
-        if not names or len(set(names)) != len(names) or any(k not in RETURNS for k in names):
-            raise ValueError(f'qp_layer: returns must be "x" or distinct names out of {RETURNS} (got {returns!r})')
-        out = _EliminatedQPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, nullspace, names, eq_rows)
-        return out[0] if isinstance(returns, str) else out
-    if nullspace and has_soft:
+    elif nullspace and has_soft:
         raise ValueError("qp_layer: nullspace=True does not take SOFT rows")
-    if isinstance(returns, str) and returns == "x":
-        return _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, nullspace)
     names = (returns,) if isinstance(returns, str) else tuple(returns)
-    if not names or len(set(names)) != len(names) or any(k not in RETURNS for k in names):
+    allowed = SOFT_RETURNS if route == "soft" else RETURNS
+    if not names or len(set(names)) != len(names) or any(k not in allowed for k in names):
+        if route == "soft":
+            raise ValueError(f'qp_layer: returns must be distinct names out of {SOFT_RETURNS} with soft_returns=True (got {returns!r})')
         raise ValueError(f'qp_layer: returns must be "x" or distinct names out of {RETURNS} (got {returns!r})')
-    if has_soft:
+    if route == "names" and has_soft:
         raise ValueError('qp_layer: returns other than "x" does not take SOFT rows: their multipliers and objective are not differentiated')
-    out = _QPLayer.apply(H, f, A, bupper, blower, ms, strict, info, dict(settings), sense, rho_soft, nullspace, names)
+    out = _QPLayer.apply(H, f, A, bupper, blower, rho_soft, ms, strict, info, dict(settings), sense, nullspace, names, route, eq_rows)
     return out[0] if isinstance(returns, str) else out
